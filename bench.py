@@ -15,6 +15,11 @@ the whole-job value sums events over ranks and takes the max step time.
 Launch (driver contract):
   python bench.py --gpus N --steps K --warmup W
   torchrun --nnodes=1 --nproc-per-node N bench.py --gpus N ...
+
+A plain run sets up, warms up, times the K steps and prints one JSON line.
+`--dump-outputs DIR` also writes the last timed step's outputs as .npy files
+(inputs and initial weights are seeded, so two builds can be compared);
+`--full` is where any secondary measurement belongs (none exists today).
 """
 from __future__ import annotations
 
@@ -73,6 +78,24 @@ def build_bench_batches(rank: int, n_windows: int, scale: str):
     return batches
 
 
+DUMP_BUDGET_BYTES = 64 * 1000 * 1000  # --dump-outputs: all files together
+
+
+def dump_outputs(out_dir: str, arrays: dict) -> None:
+    """Write each tensor as <out_dir>/<name>.npy (float32, flattened).
+
+    An array over its share of the byte budget is cut to a fixed, seeded
+    sample of its elements (same indices every run for the same shape)."""
+    os.makedirs(out_dir, exist_ok=True)
+    per_array = DUMP_BUDGET_BYTES // 4 // max(len(arrays), 1) - 64  # .npy header
+    for name, t in arrays.items():
+        a = t.detach().float().cpu().numpy().reshape(-1)
+        if a.size > per_array:
+            idx = np.random.default_rng(0).choice(a.size, size=per_array, replace=False)
+            a = a[np.sort(idx)]
+        np.save(os.path.join(out_dir, f"{name}.npy"), np.ascontiguousarray(a, dtype=np.float32))
+
+
 def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -92,9 +115,23 @@ def main() -> None:
         help="hipGraph-capture the whole training step (measured neutral at "
         "full scale — the step is kernel-bound — so off by default)",
     )
+    ap.add_argument(
+        "--dump-outputs", metavar="DIR", default=None,
+        help="after the timed steps, write what the last timed step computed "
+        "(logits, losses, updated parameters) as DIR/<name>.npy (float32)",
+    )
+    ap.add_argument(
+        "--full", action="store_true",
+        help="also run every secondary measurement; the plain run times the "
+        "headline figure only (this benchmark has no secondary measurement "
+        "yet, so the flag changes nothing today)",
+    )
     args = ap.parse_args()
 
     rank, world, local_rank = init_distributed()
+    # fixed seed: same arguments -> same initial weights, so two builds can be
+    # compared output for output (--dump-outputs); data is seeded separately
+    torch.manual_seed(0)
     has_gpu = torch.cuda.is_available()
     if has_gpu:
         torch.cuda.set_device(local_rank)
@@ -137,16 +174,21 @@ def main() -> None:
     reducer = GradAllReducer(model)
     reducer.broadcast_params(model)
 
-    def step_body(b) -> None:
+    def step_body(b) -> dict:
         node_logit, edge_logit, seq_logit = model(b)
         losses = model.loss(node_logit, edge_logit, seq_logit, b)
         opt.zero_grad(set_to_none=False)
         losses["total"].backward()
         reducer.finalize()
         opt.step()
+        out = {"node_logit": node_logit, "edge_logit": edge_logit, "seq_logit": seq_logit}
+        out.update({f"loss_{k}": v for k, v in losses.items()})
+        return {k: v.detach() for k, v in out.items() if v is not None}
+
+    last_out = [None]  # what the most recent step returned (--dump-outputs)
 
     def step(i: int) -> int:
-        step_body(batches[i % len(batches)])
+        last_out[0] = step_body(batches[i % len(batches)])
         return events_per_step[i % len(batches)]
 
     if use_graphs:
@@ -162,14 +204,16 @@ def main() -> None:
             torch.cuda.current_stream().wait_stream(side)
             torch.cuda.synchronize()
             graphs = []
+            graph_outs = []  # static output tensors each replay refills
             for b in batches:
                 g = torch.cuda.CUDAGraph()
                 with torch.cuda.graph(g):
-                    step_body(b)
+                    graph_outs.append(step_body(b))
                 graphs.append(g)
 
             def step(i: int) -> int:  # noqa: F811 - graph replay path
                 graphs[i % len(graphs)].replay()
+                last_out[0] = graph_outs[i % len(graphs)]
                 return events_per_step[i % len(batches)]
 
             if rank == 0:
@@ -208,6 +252,11 @@ def main() -> None:
     t_max = float(t_tensor[0])
     e_sum = float(e_tensor[0])
     value = e_sum / t_max
+
+    if args.dump_outputs and rank == 0 and last_out[0] is not None:
+        arrays = dict(last_out[0])
+        arrays["params"] = torch.cat([p.detach().reshape(-1).float() for p in model.parameters()])
+        dump_outputs(args.dump_outputs, arrays)
 
     if rank == 0:
         result = {

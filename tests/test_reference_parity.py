@@ -1,23 +1,19 @@
 """Parity on the reference's RECORDED benchmark artifacts (VERDICT r1 gap 1).
 
 These tests load the actual traces the upstream tracker captured in minikube
-(`/root/reference/benchmarks/m{0,1}/results/`), replay them through the
-engine, and assert the recorded attack is detected inside the recorded
-ground-truth window — the only validation data the reference ships.
-Skipped where the reference checkout is absent (e.g. on a GPU box snapshot).
+(the reference's `benchmarks/m{0,1}/results/`, stored verbatim under
+`tests/golden/reference_benchmarks/`), replay them through the engine, and
+assert the recorded attack is detected inside the recorded ground-truth
+window — the only validation data the reference ships.
 """
 from pathlib import Path
 
 import pytest
 
-REF = Path("/root/reference/benchmarks")
-
-needs_reference = pytest.mark.skipif(
-    not REF.exists(), reason="reference benchmark artifacts not present"
-)
+ROOT = Path(__file__).resolve().parent.parent
+REF = ROOT / "tests" / "golden" / "reference_benchmarks"
 
 
-@needs_reference
 @pytest.mark.parametrize("stem", ["m0", "m1"])
 def test_recorded_trace_loads_with_real_schema(stem):
     from nerrf_amd.data.trace import SYSCALL_IDS, load_jsonl
@@ -36,7 +32,6 @@ def test_recorded_trace_loads_with_real_schema(stem):
     assert all(p.endswith(".dat") for p in olds)
 
 
-@needs_reference
 @pytest.mark.parametrize("stem", ["m0", "m1"])
 def test_detects_recorded_attack_inside_ground_truth_window(stem):
     from nerrf_amd.harness.reference_parity import detect_on_recorded_run
@@ -52,7 +47,6 @@ def test_detects_recorded_attack_inside_ground_truth_window(stem):
     assert rep["latency_from_first_encrypt_s"] < 30.0
 
 
-@needs_reference
 def test_replay_recovery_emits_reference_schema(tmp_path):
     from nerrf_amd.harness.reference_parity import load_recorded_run, replay_recovery
 
@@ -70,11 +64,10 @@ def test_replay_recovery_emits_reference_schema(tmp_path):
     assert out.exists()
 
 
-@needs_reference
 def test_detection_with_vendored_checkpoint(tmp_path):
     """The trained checkpoint must not regress indicator-driven detection
     on the recorded data (model scores can only raise the alarm earlier)."""
-    ckpt = Path("checkpoints/pretrained")
+    ckpt = ROOT / "checkpoints" / "pretrained"
     if not (ckpt / "checkpoint.json").exists():
         pytest.skip("no vendored checkpoint")
     from nerrf_amd.harness.reference_parity import detect_on_recorded_run
@@ -86,12 +79,11 @@ def test_detection_with_vendored_checkpoint(tmp_path):
     assert rep["encrypted_file_recall"] == 1.0
 
 
-@needs_reference
 def test_detection_with_proc_identity_stack(monkeypatch):
     """The proc-identity stack (channel active + its checkpoint) also
     detects the recorded m0/m1 attacks inside their ground-truth windows —
     the future default-swap is CPU-validated against the only real data."""
-    ckpt = Path("checkpoints/pretrained_procid")
+    ckpt = ROOT / "checkpoints" / "pretrained_procid"
     if not (ckpt / "checkpoint.json").exists():
         pytest.skip("no proc-identity checkpoint")
     from nerrf_amd.harness.reference_parity import detect_on_recorded_run
