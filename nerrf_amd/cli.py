@@ -11,6 +11,7 @@ Commands (spec: reference ROADMAP.md:86, README.md:82 — `nerrf undo`,
                                      plan -> rollback -> sha256 verify
   nerrf train ...                    training entrypoint (= ai/train.py)
   nerrf serve --trace T              tracker-sim + streaming engine demo
+  nerrf plan-quality --states N      MCTS regret against the exhaustive plan oracle
 
 Entry point: `python -m nerrf_amd.cli <cmd>` (also installed as ./nerrf).
 """
@@ -117,7 +118,7 @@ def cmd_undo(args) -> int:
     if not det.alarm and not args.force:
         print(json.dumps({"alarm": False, "msg": "no attack detected; use --force to undo anyway"}))
         return 1
-    plan = engine.plan(det, n_sims=args.sims)
+    plan = engine.plan(det, n_sims=args.sims, planner=args.planner)
     manifest = None
     mpath = Path(args.dir, ".nerrf_manifest.json")
     if mpath.exists():
@@ -144,9 +145,29 @@ def cmd_scenario(args) -> int:
         file_kb=args.file_kb,
         device=args.device,
         n_sims=args.sims,
+        planner=args.planner,
     )
     print(json.dumps(report, indent=2))
     return 0 if report["recovered_ok"] else 2
+
+
+def cmd_plan_quality(args) -> int:
+    """MCTS regret against the exhaustive oracle on seeded planner states
+    (generator: planner/quality.py)."""
+    from .planner.quality import measure_plan_quality
+    from .planner.rewards import PlannerParams
+
+    on_cpu = args.device == "cpu"
+    # the default configuration (G=8, D=10: 9.86 M plans) is out of the CPU
+    # reference's reach, so the CPU defaults are smaller
+    groups = args.groups if args.groups is not None else (4 if on_cpu else 8)
+    depth = args.max_depth if args.max_depth is not None else (6 if on_cpu else 10)
+    params = PlannerParams(n_groups=groups, max_depth=depth)
+    sims = [int(x) for x in args.sims.split(",") if x]
+    report = measure_plan_quality(args.states, args.seed, sims=sims,
+                                  device=args.device, params=params)
+    print(json.dumps(report, indent=2))
+    return 0
 
 
 def cmd_serve(args) -> int:
@@ -261,7 +282,7 @@ def cmd_train(args, extra) -> int:
     return 0
 
 
-def main(argv=None) -> int:
+def build_parser() -> argparse.ArgumentParser:
     ap = argparse.ArgumentParser(prog="nerrf", description="nerrf-amd: undo computing engine")
     sub = ap.add_subparsers(dest="cmd", required=True)
 
@@ -282,6 +303,8 @@ def main(argv=None) -> int:
     p.add_argument("--trace", default=None, help="trace file to ingest first")
     p.add_argument("--device", default="cpu")
     p.add_argument("--sims", type=int, default=1024)
+    p.add_argument("--planner", choices=("mcts", "exact"), default="mcts",
+                   help="exact = exhaustive search over every plan")
     p.add_argument("--force", action="store_true")
     p.add_argument("--checkpoint", default=None, help="trained model checkpoint dir")
 
@@ -291,6 +314,20 @@ def main(argv=None) -> int:
     p.add_argument("--file-kb", type=int, default=32)
     p.add_argument("--device", default="cpu")
     p.add_argument("--sims", type=int, default=512)
+    p.add_argument("--planner", choices=("mcts", "exact"), default="mcts",
+                   help="exact = exhaustive search over every plan")
+
+    p = sub.add_parser("plan-quality",
+                       help="MCTS regret against the exhaustive plan oracle")
+    p.add_argument("--states", type=int, default=12)
+    p.add_argument("--seed", type=int, default=0)
+    p.add_argument("--sims", default="128,512,1024",
+                   help="comma-separated MCTS simulation budgets")
+    p.add_argument("--device", default="cpu")
+    p.add_argument("--groups", type=int, default=None,
+                   help="file groups G (default 8; 4 on cpu)")
+    p.add_argument("--max-depth", type=int, default=None,
+                   help="plan depth D (default 10; 6 on cpu)")
 
     p = sub.add_parser("serve", help="streaming engine (live tracker or trace demo)")
     p.add_argument("--trace", default=None, help="trace file (demo mode)")
@@ -316,7 +353,11 @@ def main(argv=None) -> int:
 
     sub.add_parser("train", help="training entrypoint (args passed through)")
     sub.add_parser("tune", help="hparam search (args passed through to nerrf_amd.tune)")
+    return ap
 
+
+def main(argv=None) -> int:
+    ap = build_parser()
     if argv is None:
         argv = sys.argv[1:]
     if argv and argv[0] == "train":
@@ -333,6 +374,7 @@ def main(argv=None) -> int:
         "scenario": cmd_scenario,
         "serve": cmd_serve,
         "eval": cmd_eval,
+        "plan-quality": cmd_plan_quality,
     }[args.cmd](args)
 
 

@@ -27,6 +27,7 @@ def run_scenario(
     n_sims: int = 512,
     artifacts_dir: Optional[str | Path] = None,
     model=None,
+    planner: str = "mcts",
 ) -> Dict:
     """Returns a metrics report; writes benchmark artifacts when requested."""
     from ..serve.engine import StreamingEngine
@@ -57,7 +58,7 @@ def run_scenario(
 
     # ---- phase 4: plan -----------------------------------------------------
     t_plan0 = time.perf_counter()
-    plan = engine.plan(det, n_sims=n_sims)
+    plan = engine.plan(det, n_sims=n_sims, planner=planner)
     t_plan = time.perf_counter() - t_plan0
 
     # ---- phase 5: recover (sandbox gate + live restore) --------------------

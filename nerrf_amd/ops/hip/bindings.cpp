@@ -13,6 +13,9 @@ void launch_mcts(const float*, const float*, const float*, float, float,
 void launch_eval_plans(const float*, const float*, const float*, float, float,
                        const PlannerParamsDev&, const int*, int, int, float*,
                        hipStream_t);
+void launch_plan_oracle(const float*, const float*, const float*, const float*,
+                        const float*, const PlannerParamsDev&, int, int, int,
+                        float*, int*, unsigned*, hipStream_t);
 void launch_gather_mean_fwd(const void*, const long*, const float*, void*, int,
                             int, int, bool, hipStream_t);
 void launch_gather_mean_bwd(const void*, const long*, const float*, float*,
@@ -635,6 +638,140 @@ torch::Tensor mcts_eval_plans(torch::Tensor gscore, torch::Tensor gmb,
   return out;
 }
 
+// Exhaustive plan oracle over a batch of S states (plan_oracle.hip).
+// Returns CPU tensors, one row per state and one slot per first action
+// (slot 0 = STOP, the empty plan; slot a = best plan starting with action a):
+//   [0] reward  f32 [S, n+1]  eval_plan's value of the winner (== mcts_eval_plans)
+//   [1] len     i32 [S, n+1]
+//   [2] plan    i32 [S, n+1, 16]  STOP-padded
+//   [3] meta    i64 [2]       prefix length L, prefixes per state
+std::vector<torch::Tensor> plan_oracle_search(
+    torch::Tensor gscore, torch::Tensor gmb, torch::Tensor gfiles,
+    torch::Tensor proc, torch::Tensor clean, pybind11::dict param_dict,
+    long prefix_len) {
+  auto p = params_from_dict(param_dict);
+  const torch::Tensor* ins[] = {&gscore, &gmb, &gfiles, &proc, &clean};
+  const char* names[] = {"gscore", "gmb", "gfiles", "proc", "clean"};
+  for (int i = 0; i < 5; ++i) {
+    check_gpu_contig(*ins[i], names[i]);
+    TORCH_CHECK(ins[i]->scalar_type() == torch::kFloat32, names[i],
+                " must be float32");
+  }
+  TORCH_CHECK(gscore.dim() == 2, "gscore must be [S, G]");
+  const long S = gscore.size(0);
+  const int G = p.n_groups;
+  TORCH_CHECK(S >= 1 && S <= (1 << 20), "need 1 <= S <= 2^20 states");
+  TORCH_CHECK(G >= 1, "n_groups must be >= 1");
+  TORCH_CHECK(p.max_depth >= 1, "max_depth must be >= 1");
+  TORCH_CHECK(gscore.size(1) == G && gmb.sizes() == gscore.sizes() &&
+                  gfiles.sizes() == gscore.sizes(),
+              "gscore/gmb/gfiles must all be [S, n_groups]");
+  TORCH_CHECK(proc.dim() == 1 && proc.size(0) == S && clean.dim() == 1 &&
+                  clean.size(0) == S,
+              "proc/clean must be [S]");
+  const int n = G + 2;  // non-STOP actions
+  const int depth_lim = std::min(p.max_depth, n);
+  const long kMaxPrefix = 1L << 22;
+  int L = 1;
+  long n_prefix = n;
+  if (prefix_len > 0) {
+    TORCH_CHECK(prefix_len <= depth_lim, "prefix_len must be <= min(max_depth, n)");
+    for (L = 1; L < prefix_len; ++L) n_prefix *= (n - L);
+    TORCH_CHECK(n_prefix <= kMaxPrefix, "prefix_len gives too many prefixes");
+  } else {
+    // enough work items to fill the device, but leave the search some depth
+    const int l_max = std::max(1, depth_lim - 3);
+    const long target = 65536;
+    while (L < l_max && S * n_prefix < target &&
+           n_prefix * (n - L) <= kMaxPrefix) {
+      n_prefix *= (n - L);
+      ++L;
+    }
+  }
+  TORCH_CHECK(S * n_prefix <= (1L << 26),
+              "too many work items (states x prefixes); lower prefix_len or "
+              "split the batch");
+
+  auto opts_f = gscore.options().dtype(torch::kFloat32);
+  auto opts_i = gscore.options().dtype(torch::kInt32);
+  auto item_reward = torch::empty({S, n_prefix}, opts_f);
+  auto item_len = torch::empty({S, n_prefix}, opts_i);
+  auto item_plan = torch::empty({S, n_prefix, 6}, opts_i);
+  auto stream = at::hip::getCurrentHIPStream();
+  nerrf::launch_plan_oracle(
+      gscore.data_ptr<float>(), gmb.data_ptr<float>(), gfiles.data_ptr<float>(),
+      proc.data_ptr<float>(), clean.data_ptr<float>(), p, (int)S, L,
+      (int)n_prefix, item_reward.data_ptr<float>(), item_len.data_ptr<int>(),
+      reinterpret_cast<unsigned*>(item_plan.data_ptr<int>()), stream.stream());
+  const hipError_t launch_err = hipGetLastError();
+  TORCH_CHECK(launch_err == hipSuccess, "plan oracle launch failed: ",
+              hipGetErrorString(launch_err));
+
+  // ---- reduce the prefix winners by first action (host; not hot) ----
+  auto h_reward = item_reward.cpu();
+  auto h_len = item_len.cpu();
+  auto h_plan = item_plan.cpu();
+  auto h_proc = proc.cpu();
+  auto h_clean = clean.cpu();
+  const float* hr = h_reward.data_ptr<float>();
+  const int* hl = h_len.data_ptr<int>();
+  const unsigned* hp = reinterpret_cast<const unsigned*>(h_plan.data_ptr<int>());
+  auto cpu_i = torch::TensorOptions().dtype(torch::kInt32);
+  auto win_len = torch::zeros({S, (long)n + 1}, cpu_i);
+  auto win_plan = torch::zeros({S, (long)n + 1, 16}, cpu_i);
+  int* wl = win_len.data_ptr<int>();
+  int* wp = win_plan.data_ptr<int>();
+  auto field = [](const unsigned* w, int i) {
+    return (int)((w[i / 6] >> (5 * (i % 6))) & 31u);
+  };
+  for (long s = 0; s < S; ++s) {
+    std::vector<long> best(n + 1, -1);
+    for (long i = 0; i < n_prefix; ++i) {
+      const long o = s * n_prefix + i;
+      const int len = hl[o];
+      TORCH_CHECK(len >= 1 && len <= depth_lim,
+                  "plan oracle: no finite reward under a prefix "
+                  "(non-finite planner inputs?)");
+      const int a0 = field(hp + o * 6, 0);
+      TORCH_CHECK(a0 >= 1 && a0 <= n, "plan oracle: corrupt winner");
+      const long b = best[a0];
+      // items are in lexicographic prefix order: an equal (reward, len)
+      // keeps the earlier one
+      if (b < 0 || hr[o] > hr[b] || (hr[o] == hr[b] && len < hl[b])) best[a0] = o;
+    }
+    for (int a = 1; a <= n; ++a) {
+      const long o = best[a];
+      TORCH_CHECK(o >= 0, "plan oracle: first action without a winner");
+      const long slot = s * (n + 1) + a;
+      const int len = hl[o];
+      wl[slot] = len;
+      for (int i = 0; i < len; ++i) {
+        const int act = (i < L) ? field(hp + o * 6, i) : field(hp + o * 6 + 3, i - L);
+        TORCH_CHECK(act >= 1 && act <= n, "plan oracle: corrupt winner");
+        wp[slot * 16 + i] = act;
+      }
+    }
+  }
+
+  // ---- reported rewards: eval_plan on the winners ----
+  auto d_plans = win_plan.to(gscore.device());
+  auto d_reward = torch::empty({S, (long)n + 1}, opts_f);
+  const float* pproc = h_proc.data_ptr<float>();
+  const float* pclean = h_clean.data_ptr<float>();
+  for (long s = 0; s < S; ++s) {
+    nerrf::launch_eval_plans(
+        gscore.data_ptr<float>() + s * G, gmb.data_ptr<float>() + s * G,
+        gfiles.data_ptr<float>() + s * G, pproc[s], pclean[s], p,
+        d_plans.data_ptr<int>() + s * (n + 1) * 16, n + 1, 16,
+        d_reward.data_ptr<float>() + s * (n + 1), stream.stream());
+  }
+  auto win_reward = d_reward.cpu();
+  auto meta = torch::zeros({2}, torch::TensorOptions().dtype(torch::kInt64));
+  meta.data_ptr<int64_t>()[0] = L;
+  meta.data_ptr<int64_t>()[1] = n_prefix;
+  return {win_reward, win_len, win_plan, meta};
+}
+
 }  // namespace
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
@@ -647,6 +784,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "GPU delta compaction: events -> per-node feature matrix");
   m.def("mcts_search", &mcts_search, "batched root-parallel MCTS");
   m.def("mcts_eval_plans", &mcts_eval_plans, "batch plan reward evaluation");
+  m.def("plan_oracle_search", &plan_oracle_search,
+        "exhaustive best plan per first action over a batch of states",
+        pybind11::arg("gscore"), pybind11::arg("gmb"), pybind11::arg("gfiles"),
+        pybind11::arg("proc"), pybind11::arg("clean"), pybind11::arg("params"),
+        pybind11::arg("prefix_len") = 0);
   m.def("gather_mean_fwd", &gather_mean_fwd, "weighted neighbor gather-mean");
   m.def("gather_mean_bwd", &gather_mean_bwd, "gather-mean backward");
   m.def("gather_mean_bwd_csr", &gather_mean_bwd_csr,

@@ -431,7 +431,13 @@ class StreamingEngine:
 
     # -------------------------------------------------------------------- plan
     def plan(self, det: Detection, n_sims: int = 1024, use_gpu: Optional[bool] = None,
-             model_refine: bool = True) -> PlanResult:
+             model_refine: bool = True, planner: str = "mcts",
+             max_plans: Optional[int] = None) -> PlanResult:
+        """planner="mcts" (default) searches with `n_sims` simulations;
+        planner="exact" enumerates every plan (planner/oracle.py) and raises
+        ValueError when the plan space exceeds `max_plans`."""
+        if planner not in ("mcts", "exact"):
+            raise ValueError(f"unknown planner {planner!r}: expected 'mcts' or 'exact'")
         paths = list(det.file_scores.keys())
         scores = np.array([det.file_scores[p] for p in paths], dtype=np.float64)
         mb = np.array([max(det.file_mb.get(p, 0.01), 0.01) for p in paths], dtype=np.float64)
@@ -443,13 +449,34 @@ class StreamingEngine:
                             n_groups=self.planner_params.n_groups)
         if use_gpu is None:
             use_gpu = self.device.type == "cuda"
-        if use_gpu:
+        if planner == "exact":
+            res = self._plan_exact(state, use_gpu, max_plans)
+        elif use_gpu:
             res = run_mcts_gpu(state, self.planner_params, n_sims=n_sims, device=str(self.device))
         else:
             res = run_mcts(state, self.planner_params, n_sims=n_sims)
         if model_refine and det.refine_ctx is not None and paths:
             res = self._refine_plan(res, det, state, paths, scores)
         return res
+
+    def _plan_exact(self, state, use_gpu: bool, max_plans: Optional[int]) -> PlanResult:
+        """Exhaustive planner: the oracle's plan, with the exact root action
+        values Q*(a) in place of MCTS visit statistics."""
+        from ..planner.oracle import GPU_MAX_PLANS, exhaustive_best, plans_under
+
+        params = self.planner_params
+        orc = exhaustive_best(
+            state, params, device=str(self.device) if use_gpu else "cpu",
+            max_plans=GPU_MAX_PLANS if max_plans is None else max_plans,
+        )
+        n = 2 + state.n_groups
+        ranked = sorted(
+            [(int(a), float(q), plans_under(a, n, params.max_depth))
+             for a, (q, _plan) in orc.first_action_best.items()],
+            key=lambda t: (-t[1], t[0]),
+        )
+        return PlanResult(plan=list(orc.plan), ranked_actions=ranked,
+                          root_value=float(orc.reward), simulations=int(orc.n_plans))
 
     def _refine_plan(self, res: PlanResult, det: Detection, state, paths, scores) -> PlanResult:
         """Batched counterfactual re-scoring of candidate plans through the

@@ -23,6 +23,7 @@ sources = [
     os.path.join(HIP_DIR, "stream_gemm.hip"),
     os.path.join(HIP_DIR, "rec_gemm.hip"),
     os.path.join(HIP_DIR, "mcts.hip"),
+    os.path.join(HIP_DIR, "plan_oracle.hip"),
     os.path.join(HIP_DIR, "event_scatter.hip"),
     os.path.join(HIP_DIR, "sage_fused.hip"),
     os.path.join(HIP_DIR, "sage_ln_act.hip"),
