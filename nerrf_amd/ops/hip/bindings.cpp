@@ -27,10 +27,10 @@ void launch_lstm_pointwise_fwd(const void*, const void*, const void*,
                                const void*, const void*, const float*, void*,
                                void*, void*, long, int, long, long, long,
                                bool, hipStream_t);
-void launch_lstm_pointwise_bwd(const void*, const void*, const void*,
+bool launch_lstm_pointwise_bwd(const void*, const void*, const void*,
                                const void*, const void*, const float*, void*,
-                               void*, void*, float*, long, int, long, long,
-                               bool, hipStream_t);
+                               void*, void*, float*, long, long, int, long,
+                               long, bool, hipStream_t);
 void launch_lstm_step_fused(const void*, const void*, const void*, const void*,
                             const void*, const float*, void*, void*, void*,
                             int, bool, hipStream_t);
@@ -188,10 +188,15 @@ void lstm_pointwise_fwd(torch::Tensor hg, torch::Tensor xg, torch::Tensor bias,
 
 // grad_out_t (may be empty): this timestep's dL/dh, folded in-kernel so the
 // sequence backward needs no separate elementwise add per step.
-// bias_accum (optional, may be empty): f32 [4H] accumulator the kernel
-// folds sum_b(grad_gates) into (vectorised path only) — callers then skip
-// the separate whole-tensor gg.sum(0) reduction.  Returns true when the
-// fused accumulation ran.
+// bias_accum (optional, may be empty): contiguous f32 slab [P, 4H], P >= 1.
+// The kernel runs on min(P, blocks needed) blocks and block p ADDS its
+// sum over rows of the stored grad_gates into slab row p (plain stores, no
+// atomics; rows beyond the grid are not touched), so one slab accumulates
+// over the timesteps of a sequence and the caller's bias gradient is
+// slab.sum(0) — no whole-tensor gg.sum(0) re-read.  Returns true when the
+// fused accumulation ran: it needs the vectorised path and
+// 256 % (H/V) == 0 (V = 8 for bf16, 4 for f32); otherwise the slab is left
+// untouched and false is returned.
 bool lstm_pointwise_bwd(torch::Tensor grad_h, torch::Tensor grad_out_t,
                         torch::Tensor grad_c, torch::Tensor gates_act,
                         torch::Tensor c_prev, torch::Tensor mask,
@@ -218,21 +223,20 @@ bool lstm_pointwise_bwd(torch::Tensor grad_h, torch::Tensor grad_out_t,
   long gout_stride = hdim;
   if (grad_out_t.numel()) gout_stride = row_stride_checked(grad_out_t, "grad_out_t");
   float* bias_ptr = nullptr;
-  const int v = is_bf16(grad_h) ? 8 : 4;
-  const bool vec = hdim % v == 0 && gout_stride % v == 0 && gg_stride % v == 0;
-  if (bias_accum.numel() > 0 && vec) {
+  long accum_rows = 0;
+  if (bias_accum.numel() > 0) {
     check_gpu_contig(bias_accum, "bias_accum");
-    TORCH_CHECK(bias_accum.scalar_type() == torch::kFloat32 &&
-                    bias_accum.numel() == 64 * 4 * hdim,
-                "bias_accum must be f32 [64, 4H] (striped replicas)");
+    TORCH_CHECK(bias_accum.scalar_type() == torch::kFloat32 && hdim > 0 &&
+                    bias_accum.numel() % (4 * (long)hdim) == 0,
+                "bias_accum must be a contiguous f32 slab [P, 4H]");
     bias_ptr = bias_accum.data_ptr<float>();
+    accum_rows = bias_accum.numel() / (4 * (long)hdim);
   }
-  nerrf::launch_lstm_pointwise_bwd(
+  return nerrf::launch_lstm_pointwise_bwd(
       grad_h.data_ptr(), got, grad_c.data_ptr(), gates_act.data_ptr(),
       c_prev.data_ptr(), mask_ptr, grad_gates.data_ptr(),
-      grad_c_prev.data_ptr(), grad_h_pass.data_ptr(), bias_ptr, batch, hdim,
-      gout_stride, gg_stride, is_bf16(grad_h), stream.stream());
-  return bias_ptr != nullptr;
+      grad_c_prev.data_ptr(), grad_h_pass.data_ptr(), bias_ptr, accum_rows,
+      batch, hdim, gout_stride, gg_stride, is_bf16(grad_h), stream.stream());
 }
 
 // Fused recurrent step (bf16, H == 256): h_prev @ W_hh^T + LSTM pointwise

@@ -190,8 +190,21 @@ __global__ void lstm_pointwise_fwd_vec_kernel(
   }
 }
 
-template <typename T, int V>
-__global__ void lstm_pointwise_bwd_vec_kernel(
+// ACC = true additionally folds this launch's bias-gradient partial
+// (sum over rows of the grad_gates values just stored) into an f32 slab
+// bias_accum[P, 4H], so the sequence backward never re-reads grad_gates for
+// gg.sum(0).  It relies on blockDim.x == 256 and 256 % (hdim/V) == 0: the
+// column group t % hv of a thread is then the same on every grid-stride
+// iteration and its 4*V sums stay in registers (no LDS, no atomics in the
+// row loop).  After the loop the threads of a block that share a column
+// group combine once (wave shuffle, then LDS) and block p adds the block's
+// 4H sums into slab row p with plain coalesced loads/stores: launches on one
+// stream are ordered, nobody else touches row p, and the result is bitwise
+// reproducible.  Needs gridDim.x <= P and R*4H floats of dynamic LDS (see
+// launch_bwd_vec).  ACC = false is the plain kernel.
+template <typename T, int V, bool ACC>
+__global__ void __launch_bounds__(ACC ? 256 : 1024)
+lstm_pointwise_bwd_vec_kernel(
     const T* __restrict__ grad_h, const T* __restrict__ grad_out_t,
     const T* __restrict__ grad_c, const T* __restrict__ gates_act,
     const T* __restrict__ c_prev, const float* __restrict__ mask,
@@ -199,13 +212,11 @@ __global__ void lstm_pointwise_bwd_vec_kernel(
     T* __restrict__ grad_h_pass, float* __restrict__ bias_accum,
     long batch, int hdim, long gout_stride, long gg_stride) {
   using VT = VecT<T, V>;
-  // optional fused bias-grad: per-block LDS partial of sum_b(grad_gates),
-  // atomically folded into bias_accum[4H] at block end — removes the
-  // separate 13-GB-per-direction gg re-read (gg2.sum(0)) from the step
-  extern __shared__ float bias_lds[];
-  if (bias_accum != nullptr)
-    for (int i = threadIdx.x; i < 4 * hdim; i += blockDim.x) bias_lds[i] = 0.0f;
-  if (bias_accum != nullptr) __syncthreads();
+  float s_i[V], s_f[V], s_g[V], s_o[V];
+  if constexpr (ACC) {
+#pragma unroll
+    for (int j = 0; j < V; ++j) s_i[j] = s_f[j] = s_g[j] = s_o[j] = 0.0f;
+  }
   const int hv = hdim / V;
   const long total = batch * hv;
   for (long t = blockIdx.x * (long)blockDim.x + threadIdx.x; t < total;
@@ -252,31 +263,66 @@ __global__ void lstm_pointwise_bwd_vec_kernel(
       gg_g.v[j] = from_f32<T>(d_g * (1.0f - g * g));
       gg_o.v[j] = from_f32<T>(d_o * o * (1.0f - o));
     }
+    if constexpr (ACC) {
+      // Sum the STORED (rounded) values: what gg.sum(0) would read back.
+      // The test on the pointer (never null here, but opaque to the
+      // compiler) keeps these adds in a basic block of their own: in one
+      // block with the gate arithmetic they change how that arithmetic is
+      // contracted and packed, and the stored values then differ from the
+      // plain kernel's in the last f32 bit.
+      if (bias_accum != nullptr) {
+#pragma unroll
+        for (int j = 0; j < V; ++j) {
+          s_i[j] += to_f32(gg_i.v[j]);
+          s_f[j] += to_f32(gg_f.v[j]);
+          s_g[j] += to_f32(gg_g.v[j]);
+          s_o[j] += to_f32(gg_o.v[j]);
+        }
+      }
+    }
     *reinterpret_cast<VT*>(grad_c_prev + c0) = gcp_v;
     *reinterpret_cast<VT*>(grad_h_pass + c0) = ghp_v;
     *reinterpret_cast<VT*>(grad_gates + o0) = gg_i;
     *reinterpret_cast<VT*>(grad_gates + o0 + hdim) = gg_f;
     *reinterpret_cast<VT*>(grad_gates + o0 + 2 * hdim) = gg_g;
     *reinterpret_cast<VT*>(grad_gates + o0 + 3 * hdim) = gg_o;
-    if (bias_accum != nullptr) {
+  }
+  if constexpr (ACC) {
+    // [R, 4H] block partials: one per wave, or per 256/hv thread group
+    extern __shared__ float bias_red[];
+    const int tid = threadIdx.x;
+    const int gdim = 4 * hdim;
+    // hv divides 256, so it is a power of two: lanes l and l ^ off share a
+    // column group for every off that is a multiple of hv
+    for (int off = NERRF_WAVE / 2; off >= hv; off >>= 1) {
 #pragma unroll
       for (int j = 0; j < V; ++j) {
-        atomicAdd(bias_lds + dv + j, to_f32(gg_i.v[j]));
-        atomicAdd(bias_lds + hdim + dv + j, to_f32(gg_f.v[j]));
-        atomicAdd(bias_lds + 2 * hdim + dv + j, to_f32(gg_g.v[j]));
-        atomicAdd(bias_lds + 3 * hdim + dv + j, to_f32(gg_o.v[j]));
+        s_i[j] += __shfl_xor(s_i[j], off, NERRF_WAVE);
+        s_f[j] += __shfl_xor(s_f[j], off, NERRF_WAVE);
+        s_g[j] += __shfl_xor(s_g[j], off, NERRF_WAVE);
+        s_o[j] += __shfl_xor(s_o[j], off, NERRF_WAVE);
       }
     }
-  }
-  if (bias_accum != nullptr) {
+    const bool wide = hv >= NERRF_WAVE;  // no two lanes of a wave share a group
+    const int nrep = wide ? 256 / hv : 256 / NERRF_WAVE;
+    const int rep = wide ? tid / hv : tid / NERRF_WAVE;
+    if (wide || (tid & (NERRF_WAVE - 1)) < hv) {
+      float* dst = bias_red + rep * gdim + (tid % hv) * V;
+#pragma unroll
+      for (int j = 0; j < V; ++j) {
+        dst[j] = s_i[j];
+        dst[hdim + j] = s_f[j];
+        dst[2 * hdim + j] = s_g[j];
+        dst[3 * hdim + j] = s_o[j];
+      }
+    }
     __syncthreads();
-    // 64 striped replicas: ~8k blocks all adding to ONE [4H] vector
-    // serialize on the per-address atomic queues (~100 us/launch measured);
-    // striping by block id cuts each address's chain 64x.  The caller sums
-    // the [64, 4H] buffer once per direction.
-    float* rep = bias_accum + (long)(blockIdx.x & 63) * (4 * hdim);
-    for (int i = threadIdx.x; i < 4 * hdim; i += blockDim.x)
-      if (bias_lds[i] != 0.0f) atomicAdd(rep + i, bias_lds[i]);
+    float* row = bias_accum + (long)blockIdx.x * gdim;
+    for (int i = tid; i < gdim; i += 256) {
+      float acc = bias_red[i];
+      for (int r = 1; r < nrep; ++r) acc += bias_red[r * gdim + i];
+      row[i] += acc;
+    }
   }
 }
 
@@ -288,12 +334,20 @@ template __global__ void lstm_pointwise_fwd_vec_kernel<__hip_bfloat16, 8>(
 template __global__ void lstm_pointwise_fwd_vec_kernel<float, 4>(
     const float*, const float*, const float*, const float*, const float*,
     const float*, float*, float*, float*, long, int, long, long, long);
-template __global__ void lstm_pointwise_bwd_vec_kernel<__hip_bfloat16, 8>(
+template __global__ void lstm_pointwise_bwd_vec_kernel<__hip_bfloat16, 8, false>(
     const __hip_bfloat16*, const __hip_bfloat16*, const __hip_bfloat16*,
     const __hip_bfloat16*, const __hip_bfloat16*, const float*,
     __hip_bfloat16*, __hip_bfloat16*, __hip_bfloat16*, float*, long, int,
     long, long);
-template __global__ void lstm_pointwise_bwd_vec_kernel<float, 4>(
+template __global__ void lstm_pointwise_bwd_vec_kernel<float, 4, false>(
+    const float*, const float*, const float*, const float*, const float*,
+    const float*, float*, float*, float*, float*, long, int, long, long);
+template __global__ void lstm_pointwise_bwd_vec_kernel<__hip_bfloat16, 8, true>(
+    const __hip_bfloat16*, const __hip_bfloat16*, const __hip_bfloat16*,
+    const __hip_bfloat16*, const __hip_bfloat16*, const float*,
+    __hip_bfloat16*, __hip_bfloat16*, __hip_bfloat16*, float*, long, int,
+    long, long);
+template __global__ void lstm_pointwise_bwd_vec_kernel<float, 4, true>(
     const float*, const float*, const float*, const float*, const float*,
     const float*, float*, float*, float*, float*, long, int, long, long);
 
@@ -370,27 +424,67 @@ void launch_lstm_pointwise_fwd(const void* hg, const void* xg, const void* bias,
   }
 }
 
-void launch_lstm_pointwise_bwd(const void* grad_h, const void* grad_out_t,
+// Vectorised backward launch.  With a bias slab (accum != nullptr,
+// accum_rows = P >= 1) the accumulating instantiation runs on
+// min(P, blocks needed) blocks — block p owns slab row p, rows beyond the
+// grid are not touched.
+template <typename T, int V>
+static void launch_bwd_vec(const void* grad_h, const void* grad_out_t,
+                           const void* grad_c, const void* gates_act,
+                           const void* c_prev, const float* mask,
+                           void* grad_gates, void* grad_c_prev,
+                           void* grad_h_pass, float* accum, long accum_rows,
+                           long batch, int hdim, long gout_stride,
+                           long gg_stride, hipStream_t s) {
+  const int block = 256;  // the accumulating kernel relies on 256
+  const int hv = hdim / V;
+  if (accum != nullptr) {
+    long blocks = (batch * hv + block - 1) / block;
+    if (blocks < 1) blocks = 1;
+    const int grid = (int)(blocks < accum_rows ? blocks : accum_rows);
+    // one [4H] partial per wave (hv < 64) or per 256/hv thread group
+    const int nrep = hv >= NERRF_WAVE ? block / hv : block / NERRF_WAVE;
+    const size_t lds = (size_t)nrep * 4 * hdim * sizeof(float);
+    lstm_pointwise_bwd_vec_kernel<T, V, true><<<grid, block, lds, s>>>(
+        (const T*)grad_h, (const T*)grad_out_t, (const T*)grad_c,
+        (const T*)gates_act, (const T*)c_prev, mask, (T*)grad_gates,
+        (T*)grad_c_prev, (T*)grad_h_pass, accum, batch, hdim, gout_stride,
+        gg_stride);
+    return;
+  }
+  const int grid = grid_elems(batch * hv, block);
+  lstm_pointwise_bwd_vec_kernel<T, V, false><<<grid, block, 0, s>>>(
+      (const T*)grad_h, (const T*)grad_out_t, (const T*)grad_c,
+      (const T*)gates_act, (const T*)c_prev, mask, (T*)grad_gates,
+      (T*)grad_c_prev, (T*)grad_h_pass, nullptr, batch, hdim, gout_stride,
+      gg_stride);
+}
+
+// Returns true when the bias-gradient partial was folded into bias_accum
+// ([accum_rows, 4H] f32).  That needs the vectorised path and
+// 256 % (hdim/V) == 0; otherwise the plain kernel runs and the slab is left
+// untouched (the caller then reduces grad_gates itself).
+bool launch_lstm_pointwise_bwd(const void* grad_h, const void* grad_out_t,
                                const void* grad_c, const void* gates_act,
                                const void* c_prev, const float* mask,
                                void* grad_gates, void* grad_c_prev,
                                void* grad_h_pass, float* bias_accum,
-                               long batch, int hdim, long gout_stride,
-                               long gg_stride, bool bf16, hipStream_t s) {
+                               long accum_rows, long batch, int hdim,
+                               long gout_stride, long gg_stride, bool bf16,
+                               hipStream_t s) {
   const int block = 256;
   const int v = bf16 ? 8 : 4;
   const bool vec = hdim % v == 0 && gout_stride % v == 0 && gg_stride % v == 0;
+  const bool acc = vec && bias_accum != nullptr && accum_rows >= 1 &&
+                   block % (hdim / v) == 0;
+  float* accum = acc ? bias_accum : nullptr;
   if (bf16) {
     if (vec) {
-      const int grid = grid_elems(batch * (hdim / v), block);
-      lstm_pointwise_bwd_vec_kernel<__hip_bfloat16, 8>
-          <<<grid, block, bias_accum ? 4 * hdim * sizeof(float) : 0, s>>>(
-          (const __hip_bfloat16*)grad_h, (const __hip_bfloat16*)grad_out_t,
-          (const __hip_bfloat16*)grad_c, (const __hip_bfloat16*)gates_act,
-          (const __hip_bfloat16*)c_prev, mask, (__hip_bfloat16*)grad_gates,
-          (__hip_bfloat16*)grad_c_prev, (__hip_bfloat16*)grad_h_pass,
-          bias_accum, batch, hdim, gout_stride, gg_stride);
-      return;
+      launch_bwd_vec<__hip_bfloat16, 8>(
+          grad_h, grad_out_t, grad_c, gates_act, c_prev, mask, grad_gates,
+          grad_c_prev, grad_h_pass, accum, accum_rows, batch, hdim,
+          gout_stride, gg_stride, s);
+      return acc;
     }
     const int grid = grid_elems(batch * hdim, block);
     lstm_pointwise_bwd_kernel<__hip_bfloat16><<<grid, block, 0, s>>>(
@@ -401,14 +495,11 @@ void launch_lstm_pointwise_bwd(const void* grad_h, const void* grad_out_t,
         gout_stride, gg_stride);
   } else {
     if (vec) {
-      const int grid = grid_elems(batch * (hdim / v), block);
-      lstm_pointwise_bwd_vec_kernel<float, 4>
-          <<<grid, block, bias_accum ? 4 * hdim * sizeof(float) : 0, s>>>(
-          (const float*)grad_h, (const float*)grad_out_t, (const float*)grad_c,
-          (const float*)gates_act, (const float*)c_prev, mask,
-          (float*)grad_gates, (float*)grad_c_prev, (float*)grad_h_pass,
-          bias_accum, batch, hdim, gout_stride, gg_stride);
-      return;
+      launch_bwd_vec<float, 4>(
+          grad_h, grad_out_t, grad_c, gates_act, c_prev, mask, grad_gates,
+          grad_c_prev, grad_h_pass, accum, accum_rows, batch, hdim,
+          gout_stride, gg_stride, s);
+      return acc;
     }
     const int grid = grid_elems(batch * hdim, block);
     lstm_pointwise_bwd_kernel<float><<<grid, block, 0, s>>>(
@@ -417,6 +508,7 @@ void launch_lstm_pointwise_bwd(const void* grad_h, const void* grad_out_t,
         (float*)grad_c_prev, (float*)grad_h_pass, batch, hdim, gout_stride,
         gg_stride);
   }
+  return false;
 }
 
 }  // namespace nerrf

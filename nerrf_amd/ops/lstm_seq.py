@@ -137,6 +137,19 @@ def _dir_forward(ext, xg, h0, c0, w_hh, bias, mask, reverse, infer, h_all):
     return c_all, gates_all
 
 
+# Rows P of the f32 bias-gradient slab [P, 4H] that the backward pointwise
+# kernel accumulates into; the kernel then runs on min(P, blocks needed)
+# blocks.  2048 = 256 CUs x 8 blocks, the fastest of 512..8192 at B=64k
+# (tools/bias_slab_ab.py; profiles/PROFILES.md, "Bias-gradient slab").
+_BIAS_SLAB_ROWS = 2048
+
+
+def _bias_slab_rows(batch: int, hdim: int, dt: torch.dtype) -> int:
+    vec = 8 if dt == torch.bfloat16 else 4  # elements per thread (16 B)
+    blocks = -(-batch * max(hdim // vec, 1) // 256)  # 256-thread blocks
+    return max(1, min(_BIAS_SLAB_ROWS, blocks))
+
+
 def _dir_backward(ext, grad_out, gates_all, h_flat, c_all, h0, c0, w_hh,
                   mask, reverse, gg_out=None):
     """One direction's backward.
@@ -204,13 +217,15 @@ def _dir_backward(ext, grad_out, gates_all, h_flat, c_all, h0, c0, w_hh,
             grad_whh = torch.mm(gg2.t(), h0.to(dt))
         grad_bias = gg2.sum(dim=0)
         return grad_gates_all, grad_h, grad_c, grad_whh, grad_bias
-    # opt-in: in-kernel bias-grad accumulation (NERRF_FUSED_BIAS=1) removes
-    # the gg.sum(0) re-reads but the LDS atomicAdds cost the bwd pointwise
-    # kernel ~+105 ms/step at production shapes (A/B: 244.0 vs 349.3 ms) —
-    # a measured negative on CDNA4; the separate reduction stays default
+    # in-kernel bias-grad accumulation: every step's pointwise kernel adds
+    # its sum over rows of grad_gates into an f32 slab [P, 4H] (block p owns
+    # row p; register sums, plain stores, no atomics), so the four
+    # whole-history gg2.sum(0) re-reads per step disappear.
+    # NERRF_FUSED_BIAS=0 keeps the separate reduction for A/B runs.
     bias_accum = (
-        torch.zeros(64, gdim, device=dev, dtype=torch.float32)
-        if ext is not None and os.environ.get("NERRF_FUSED_BIAS", "0") == "1"
+        torch.zeros(_bias_slab_rows(batch, hdim, dt), gdim, device=dev,
+                    dtype=torch.float32)
+        if ext is not None and os.environ.get("NERRF_FUSED_BIAS", "1") == "1"
         else None
     )
     bias_fused = bias_accum is not None
@@ -255,7 +270,12 @@ def _dir_backward(ext, grad_out, gates_all, h_flat, c_all, h0, c0, w_hh,
                 ext.rec_gemm_dgrad(gg_t, w_hh_t_d, grad_h_pass, gh_buf)
                 grad_h = gh_buf
             else:
-                grad_h = torch.addmm(grad_h_pass, gg_t, w_hh)
+                # in place: an out-of-place addmm first copies its 2-D
+                # `self` into a fresh output (33 MB each way per step);
+                # the kernel's pass-through buffer becomes the next grad_h
+                # and the old grad_h the next pass-through target
+                grad_h_pass.addmm_(gg_t, w_hh)
+                grad_h, grad_h_pass = grad_h_pass, grad_h
         else:
             gg, gcp, ghp = _ref.lstm_pointwise_bwd_ref(
                 grad_h + grad_out[ti], grad_c, gates_all[ti], c_in,
