@@ -4,11 +4,12 @@ Spec (reference docs architecture.mdx:55-59): bidirectional, 256 hidden,
 2 layers, input = last 100 events per file, F1 >= 0.95 target.
 
 MI355X-first structure: the input projection for ALL timesteps is one large
-GEMM (hipBLASLt via torch.matmul — a plain library GEMM), and the recurrent
-part per timestep goes through `nerrf_amd.ops.lstm_cell`, the fused
-(h @ W_hh + gates-pointwise + state update) op backed by the hand-written
-CDNA4 HIP kernel on GPU.  Variable lengths are handled with masked state
-updates so the whole batch stays dense — no PackedSequence host logic.
+GEMM (hipBLASLt via torch.matmul — a plain library GEMM), and the
+recurrence of a whole layer, both directions, goes through
+`nerrf_amd.ops.lstm_seq.lstm_bilayer2`, the sequence op backed by the
+hand-written CDNA4 HIP step kernels on GPU.  Variable lengths are handled
+with masked state updates so the whole batch stays dense — no
+PackedSequence host logic.
 """
 from __future__ import annotations
 
@@ -18,6 +19,7 @@ import torch
 import torch.nn as nn
 
 from ..ops import lstm_sequence
+from ..ops.lstm_seq import lstm_bilayer2
 
 
 @dataclass
@@ -79,14 +81,10 @@ class BiLSTMDetector(nn.Module):
 
     def forward(self, feats: torch.Tensor, lengths: torch.Tensor) -> torch.Tensor:
         """feats: [B, T, E]; lengths: [B] -> per-sequence logit [B]."""
-        from ..ops.lstm_seq import lstm_bilayer
-
         b, t, _ = feats.shape
         ar = torch.arange(t, device=feats.device)
         mask = (ar.unsqueeze(1) < lengths.unsqueeze(0)).to(feats.dtype)  # [T, B]
         h = feats.transpose(0, 1).contiguous()  # time-major [T, B, E]
-        from ..ops.lstm_seq import lstm_bilayer2
-
         for layer in self.dirs:
             f, r = layer[0], layer[1]
             # both directions in ONE projection GEMM ([M,K] x [K, 2*4H]:

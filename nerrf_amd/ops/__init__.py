@@ -17,6 +17,7 @@ from typing import Optional, Tuple
 import torch
 
 from . import reference as _ref
+from .lstm_seq import lstm_sequence  # noqa: F401 (re-export)
 from .native import get_native, native_available  # noqa: F401 (re-export)
 
 __all__ = ["gather_mean", "lstm_cell", "lstm_sequence", "native_available"]
@@ -159,9 +160,6 @@ def lstm_cell(
     return _LSTMCellFn.apply(
         xg.contiguous(), h.contiguous(), c.contiguous(), w_hh, b, m
     )
-
-
-from .lstm_seq import lstm_sequence  # noqa: E402  (re-export)
 
 
 def sage_encode_fused(gnn, x, nbr_idx, nbr_w):

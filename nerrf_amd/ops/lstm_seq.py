@@ -1,19 +1,36 @@
 """Time-major fused LSTM sequence ops.
 
 One autograd Function per (layer, direction) — or per bidirectional layer —
-covering all T timesteps:
-  forward : per step exactly 1 hipBLASLt GEMM (h @ W_hh^T, beta=0) and 1 fused
-            HIP kernel (add xg + bias, 4-gate pointwise, masked state update)
-            writing straight into time-major output buffers;
-  backward: per step 1 fused gate-gradient kernel + 1 GEMM, then the weight
-            gradients as TWO large batched GEMMs over all timesteps
-            (grad_gates [T*B,4H]^T @ h_in [T*B,H]) and one reduction for bias.
+covering all T timesteps.  Each direction picks ONE step path up front
+(`_dir_forward` / `_dir_backward`) and runs one timestep loop:
 
-The bidirectional layer op (`lstm_bilayer`) runs both directions into ONE
-[T, B, 2H] buffer using the kernels' row-stride arguments: no `torch.cat`
-on the forward path (2.3 ms/window of strided CatArrayBatchedCopy at serving
-shapes) and a contiguous incoming gradient on the backward path (no
-narrow+contiguous copies of the per-direction grads).
+  forward
+    reference : pure PyTorch (CPU tensors).
+    rec-fused : one launch per step, GEMM + pointwise (lstm_rec_fused.hip).
+                Default at inference; bf16, H=256, contiguous W_hh only.
+    split     : per step 1 GEMM (h @ W_hh^T: rec_gemm.hip where its stride
+                conditions hold, else hipBLASLt) and 1 fused HIP kernel (add
+                xg + bias, 4-gate pointwise, masked state update) writing
+                straight into time-major output buffers.  Default in training.
+  backward
+    reference : pure PyTorch (CPU tensors).
+    rec-fused : gate grads + grad_h GEMM in one launch per step.
+    split     : per step 1 fused gate-gradient kernel (which also folds the
+                bias gradient into an f32 slab) + 1 in-place addmm.  Default.
+  then, on every path, the weight gradients as two large batched GEMMs over
+  all timesteps (grad_gates [T*B,4H]^T @ h_in [T*B,H]) and the bias gradient.
+
+Flags (docs/flags.md), read once per forward / backward call:
+  NERRF_REC_FUSED   infer (default) | 1 | 0 — where the rec-fused path runs
+  NERRF_REC_GEMM    1 (default) | 0 — rec_gemm.hip vs hipBLASLt in the split fwd
+  NERRF_FUSED_BIAS  1 (default) | 0 — in-kernel bias-grad slab in the split bwd
+  NERRF_STREAM_DIRS 0 (default) | 1 — `lstm_bilayer2` inference on two streams
+
+The bidirectional layer ops (`lstm_bilayer`, `lstm_bilayer2`) run both
+directions into ONE [T, B, 2H] buffer using the kernels' row-stride
+arguments: no `torch.cat` on the forward path (2.3 ms/window of strided
+CatArrayBatchedCopy at serving shapes) and a contiguous incoming gradient on
+the backward path (no narrow+contiguous copies of the per-direction grads).
 
 This removes the per-step elementwise adds / stacks / reduces that dominated
 the naive schedule (profiles/: 84% of busy time before the restructure).
@@ -21,6 +38,7 @@ Everything is time-major [T, B, ...]; the model transposes once per sequence.
 """
 from __future__ import annotations
 
+import contextlib
 import os
 from typing import Optional
 
@@ -28,6 +46,20 @@ import torch
 
 from . import reference as _ref
 from .native import get_native
+
+
+def _mfma_eligible(dt: torch.dtype, hdim: int, w_hh: torch.Tensor) -> bool:
+    """Shape contract of the MFMA step kernels (lstm_rec_fused.hip,
+    rec_gemm.hip)."""
+    return dt == torch.bfloat16 and hdim == 256 and w_hh.is_contiguous()
+
+
+def _rec_fused(infer: bool) -> bool:
+    """Whether NERRF_REC_FUSED asks for the fused recurrent step:
+    "infer" (default) = forward passes that save nothing for a backward,
+    "1" = everywhere, anything else = nowhere."""
+    mode = os.environ.get("NERRF_REC_FUSED", "infer")
+    return mode == "1" or (mode == "infer" and infer)
 
 
 def _dir_forward(ext, xg, h0, c0, w_hh, bias, mask, reverse, infer, h_all):
@@ -41,90 +73,10 @@ def _dir_forward(ext, xg, h0, c0, w_hh, bias, mask, reverse, infer, h_all):
     gates_all = torch.empty(
         0 if infer else t_len, batch, gdim, device=dev, dtype=dt
     )
-    g_none = torch.empty(0, device=dev, dtype=dt)
-    h = h0.contiguous()
-    c = c0.contiguous()
-    steps = range(t_len - 1, -1, -1) if reverse else range(t_len)
-    if ext is not None:
-        empty_mask = torch.empty(0, device=dev)
-        # Fused recurrent step (lstm_rec_fused.hip): keeps the [B, 4H]
-        # pre-activation slab out of HBM (one launch per timestep).
-        # Measured: TRAINING at parity fwd / -13% bwd vs split (LDS
-        # transpose stage caps occupancy — profiles/PROFILES.md ladder),
-        # but INFERENCE 16% faster per serving window (no gate store:
-        # 394 -> ~100 MB/timestep).  Default: fused on the infer path,
-        # split for training; NERRF_REC_FUSED=1/0 forces either.
-        mode = os.environ.get("NERRF_REC_FUSED", "infer")
-        rec_fused = (
-            hasattr(ext, "lstm_rec_fwd")
-            and (mode == "1" or (mode == "infer" and infer))
-            and dt == torch.bfloat16 and hdim == 256 and w_hh.is_contiguous()
-        )
-        if rec_fused:
-            bias_c = bias.contiguous()
-            for ti in steps:
-                ext.lstm_rec_fwd(
-                    h, w_hh, xg[ti], bias_c, c,
-                    mask[ti] if mask is not None else empty_mask,
-                    h_all[ti], c_all[ti],
-                    g_none if infer else gates_all[ti],
-                )
-                h = h_all[ti]
-                c = c_all[ti]
-            return c_all, gates_all
-        # The fully-fused MFMA step (lstm_step_fused.hip) is numerically
-        # validated but measured slower than hipBLASLt-GEMM + fused
-        # pointwise (profiles/PROFILES.md has the ladder); opt-in, and it
-        # needs a contiguous output slab.
-        fused = (
-            os.environ.get("NERRF_FUSED_LSTM", "0") == "1"
-            and dt == torch.bfloat16 and hdim == 256 and w_hh.is_contiguous()
-            and h_all.is_contiguous()
-        )
-        if fused:
-            bias_c = bias.contiguous()
-            # k-slice-contiguous weight tiling (see lstm_step_fused.hip)
-            w_tiled = w_hh.reshape(gdim, hdim // 32, 32).permute(1, 0, 2).contiguous()
-            g_scratch = (
-                torch.empty(batch, gdim, device=dev, dtype=dt) if infer else None
-            )
-            for ti in steps:
-                ext.lstm_step_fused(
-                    h, w_tiled, xg[ti], bias_c, c,
-                    mask[ti] if mask is not None else empty_mask,
-                    h_all[ti], c_all[ti],
-                    g_scratch if infer else gates_all[ti], False,
-                )
-                h = h_all[ti]
-                c = c_all[ti]
-        else:
-            w_hh_t = w_hh.t().contiguous()
-            hg = torch.empty(batch, gdim, device=dev, dtype=dt)
-            # dedicated NT MFMA kernel for the [B,256]x[1024,256]^T step
-            # (rec_gemm.hip): hipBLASLt's tuned tiles run this shape at
-            # ~2.2 TB/s effective (profiles/train_kstats_r02.txt) —
-            # K=256 is too short to hide latency and the C epilogue
-            # dominates.  NERRF_REC_GEMM=0 falls back to hipBLASLt.
-            use_rg = (
-                hasattr(ext, "rec_gemm_fwd")
-                and os.environ.get("NERRF_REC_GEMM", "1") == "1"
-                and dt == torch.bfloat16 and hdim == 256 and gdim == 1024
-                and w_hh.is_contiguous()
-            )
-            for ti in steps:
-                if use_rg and h.stride(1) == 1 and h.stride(0) % 8 == 0:
-                    ext.rec_gemm_fwd(h, w_hh, hg)
-                else:
-                    torch.mm(h, w_hh_t, out=hg)
-                ext.lstm_pointwise_fwd(
-                    hg, xg[ti], bias, c, h,
-                    mask[ti] if mask is not None else empty_mask,
-                    h_all[ti], c_all[ti], g_none if infer else gates_all[ti],
-                )
-                h = h_all[ti]
-                c = c_all[ti]
-    else:
-        for ti in steps:
+
+    # each step(ti, h, c) consumes the previous state and returns the new one
+    if ext is None:
+        def step(ti, h, c):
             gates_pre = torch.addmm(bias, h, w_hh.t()) + xg[ti]
             h_new, c_new, g_act = _ref.lstm_pointwise_fwd_ref(
                 gates_pre, c, h, mask[ti] if mask is not None else None
@@ -133,7 +85,57 @@ def _dir_forward(ext, xg, h0, c0, w_hh, bias, mask, reverse, infer, h_all):
             c_all[ti] = c_new
             if not infer:
                 gates_all[ti] = g_act
-            h, c = h_new, c_new
+            return h_new, c_new
+    else:
+        mfma = _mfma_eligible(dt, hdim, w_hh)
+        g_none = torch.empty(0, device=dev, dtype=dt)
+        empty_mask = torch.empty(0, device=dev)
+        if mfma and _rec_fused(infer):
+            # Fused recurrent step (lstm_rec_fused.hip): keeps the [B, 4H]
+            # pre-activation slab out of HBM (one launch per timestep).
+            # Measured: TRAINING at parity fwd / -13% bwd vs split (LDS
+            # transpose stage caps occupancy — profiles/PROFILES.md ladder),
+            # but INFERENCE 16% faster per serving window (no gate store:
+            # 394 -> ~100 MB/timestep).  Default: fused on the infer path,
+            # split for training; NERRF_REC_FUSED=1/0 forces either.
+            bias_c = bias.contiguous()
+
+            def step(ti, h, c):
+                h_t, c_t = h_all[ti], c_all[ti]
+                ext.lstm_rec_fwd(
+                    h, w_hh, xg[ti], bias_c, c,
+                    mask[ti] if mask is not None else empty_mask,
+                    h_t, c_t, g_none if infer else gates_all[ti],
+                )
+                return h_t, c_t
+        else:
+            w_hh_t = w_hh.t().contiguous()
+            hg = torch.empty(batch, gdim, device=dev, dtype=dt)
+            # dedicated NT MFMA kernel for the [B,256]x[1024,256]^T step
+            # (rec_gemm.hip): hipBLASLt's tuned tiles run this shape at
+            # ~2.2 TB/s effective (profiles/train_kstats_r02.txt) —
+            # K=256 is too short to hide latency and the C epilogue
+            # dominates.  NERRF_REC_GEMM=0 falls back to hipBLASLt.
+            use_rg = mfma and os.environ.get("NERRF_REC_GEMM", "1") == "1"
+
+            def step(ti, h, c):
+                # per step: h goes from h0 to a slab view after the first
+                if use_rg and h.stride(1) == 1 and h.stride(0) % 8 == 0:
+                    ext.rec_gemm_fwd(h, w_hh, hg)
+                else:
+                    torch.mm(h, w_hh_t, out=hg)
+                h_t, c_t = h_all[ti], c_all[ti]
+                ext.lstm_pointwise_fwd(
+                    hg, xg[ti], bias, c, h,
+                    mask[ti] if mask is not None else empty_mask,
+                    h_t, c_t, g_none if infer else gates_all[ti],
+                )
+                return h_t, c_t
+
+    h = h0.contiguous()
+    c = c0.contiguous()
+    for ti in (range(t_len - 1, -1, -1) if reverse else range(t_len)):
+        h, c = step(ti, h, c)
     return c_all, gates_all
 
 
@@ -148,6 +150,35 @@ def _bias_slab_rows(batch: int, hdim: int, dt: torch.dtype) -> int:
     vec = 8 if dt == torch.bfloat16 else 4  # elements per thread (16 B)
     blocks = -(-batch * max(hdim // vec, 1) // 256)  # 256-thread blocks
     return max(1, min(_BIAS_SLAB_ROWS, blocks))
+
+
+def _weight_grads(grad_gates_all, h_flat, h0, reverse, bias_slab):
+    """(grad_whh, grad_bias) over all timesteps.  The h input of step ti is
+    the hidden history shifted by one step, whose bulk is a contiguous-rank
+    slice of h_flat — two GEMMs (bulk + the h0 boundary row) instead of
+    materialising a shifted copy of the whole history.  `bias_slab` is the
+    f32 slab every step accumulated into, or None to reduce grad_gates."""
+    t_len, batch, gdim = grad_gates_all.shape
+    dt = grad_gates_all.dtype
+    gg2 = grad_gates_all.reshape(t_len * batch, gdim)
+    if t_len > 1:
+        if reverse:
+            bulk_gg = grad_gates_all[:-1].reshape((t_len - 1) * batch, gdim)
+            bulk_h = h_flat[batch:]
+            edge_gg = grad_gates_all[t_len - 1]
+        else:
+            bulk_gg = grad_gates_all[1:].reshape((t_len - 1) * batch, gdim)
+            bulk_h = h_flat[: (t_len - 1) * batch]
+            edge_gg = grad_gates_all[0]
+        grad_whh = torch.mm(bulk_gg.t(), bulk_h)
+        grad_whh = torch.addmm(grad_whh, edge_gg.t(), h0.to(dt))
+    else:
+        grad_whh = torch.mm(gg2.t(), h0.to(dt))
+    grad_bias = (
+        bias_slab.sum(dim=0).to(dt) if bias_slab is not None
+        else gg2.sum(dim=0)
+    )
+    return grad_whh, grad_bias
 
 
 def _dir_backward(ext, grad_out, gates_all, h_flat, c_all, h0, c0, w_hh,
@@ -171,146 +202,98 @@ def _dir_backward(ext, grad_out, gates_all, h_flat, c_all, h0, c0, w_hh,
         gg_out if gg_out is not None
         else torch.empty(t_len, batch, gdim, device=dev, dtype=dt)
     )
+    # running state and its ping-pong partners: a native step writes the
+    # new grad_h / grad_c into the spare pair, which the loop then swaps in
     grad_h = torch.zeros(batch, hdim, device=dev, dtype=dt)
     grad_c = torch.zeros(batch, hdim, device=dev, dtype=dt)
-    grad_h_pass = torch.empty(batch, hdim, device=dev, dtype=dt)
-    grad_c_prev = torch.empty(batch, hdim, device=dev, dtype=dt)
+    spare_h = torch.empty(batch, hdim, device=dev, dtype=dt)
+    spare_c = torch.empty(batch, hdim, device=dev, dtype=dt)
+    slab, slab_used = None, False  # f32 bias-grad slab of the split path
 
-    # iterate in the opposite order of forward
-    steps = range(t_len) if reverse else range(t_len - 1, -1, -1)
-    empty_mask = torch.empty(0, device=dev)
-    rec_fused = (
-        ext is not None
-        and hasattr(ext, "lstm_rec_bwd")
-        and os.environ.get("NERRF_REC_FUSED", "infer") == "1"
-        and dt == torch.bfloat16 and hdim == 256
-    )
-    if rec_fused:
-        # fused gate grads + in-launch grad_h GEMM (lstm_rec_fused.hip):
-        # grad_gates goes to HBM once, the addmm disappears
-        w_hh_t = w_hh.t().contiguous()
-        grad_h_next = torch.empty(batch, hdim, device=dev, dtype=dt)
-        for ti in steps:
-            first = (ti == t_len - 1) if reverse else (ti == 0)
-            c_in = c0 if first else (c_all[ti + 1] if reverse else c_all[ti - 1])
-            ext.lstm_rec_bwd(
-                grad_h.contiguous(), grad_out[ti], grad_c.contiguous(),
-                gates_all[ti], c_in.contiguous(), w_hh_t,
-                mask[ti] if mask is not None else empty_mask,
-                grad_gates_all[ti], grad_c_prev, grad_h_next,
-            )
-            grad_h, grad_h_next = grad_h_next, grad_h
-            grad_c, grad_c_prev = grad_c_prev, grad_c
-        gg2 = grad_gates_all.reshape(t_len * batch, gdim)
-        if t_len > 1:
-            if reverse:
-                bulk_gg = grad_gates_all[:-1].reshape((t_len - 1) * batch, gdim)
-                bulk_h = h_flat[batch:]
-                edge_gg = grad_gates_all[t_len - 1]
-            else:
-                bulk_gg = grad_gates_all[1:].reshape((t_len - 1) * batch, gdim)
-                bulk_h = h_flat[: (t_len - 1) * batch]
-                edge_gg = grad_gates_all[0]
-            grad_whh = torch.mm(bulk_gg.t(), bulk_h)
-            grad_whh = torch.addmm(grad_whh, edge_gg.t(), h0.to(dt))
-        else:
-            grad_whh = torch.mm(gg2.t(), h0.to(dt))
-        grad_bias = gg2.sum(dim=0)
-        return grad_gates_all, grad_h, grad_c, grad_whh, grad_bias
-    # in-kernel bias-grad accumulation: every step's pointwise kernel adds
-    # its sum over rows of grad_gates into an f32 slab [P, 4H] (block p owns
-    # row p; register sums, plain stores, no atomics), so the four
-    # whole-history gg2.sum(0) re-reads per step disappear.
-    # NERRF_FUSED_BIAS=0 keeps the separate reduction for A/B runs.
-    bias_accum = (
-        torch.zeros(_bias_slab_rows(batch, hdim, dt), gdim, device=dev,
-                    dtype=torch.float32)
-        if ext is not None and os.environ.get("NERRF_FUSED_BIAS", "1") == "1"
-        else None
-    )
-    bias_fused = bias_accum is not None
-    # dedicated dgrad kernel for grad_h = grad_h_pass + gg @ W_hh
-    # (rec_gemm.hip, NT form with K/N swapped).  Measured 0.31x of
-    # hipBLASLt addmm at M=64k (tools/rec_gemm_ab.py: 172.9 vs 54.1 us —
-    # the K=1024 chunk-staging barriers serialise what blas pipelines, and
-    # addmm already runs at 3.7 TB/s on this shape), so OPT-IN
-    # (NERRF_REC_DGRAD=1) as the in-tree baseline for a pipelined rewrite.
-    use_rg_d = (
-        ext is not None
-        and hasattr(ext, "rec_gemm_dgrad")
-        and os.environ.get("NERRF_REC_DGRAD", "0") == "1"
-        and dt == torch.bfloat16 and hdim == 256 and gdim == 1024
-    )
-    if use_rg_d:
-        w_hh_t_d = w_hh.t().contiguous()
-        gh_buf = torch.empty(batch, hdim, device=dev, dtype=dt)
-    for ti in steps:
-        # c/h input of step ti = previous step's output (or h0/c0 at start)
-        first = (ti == t_len - 1) if reverse else (ti == 0)
-        if first:
-            c_in = c0
-        else:
-            c_in = c_all[ti + 1] if reverse else c_all[ti - 1]
-        if ext is not None:
-            # grad_out[ti] is folded inside the kernel (no separate add),
-            # and so is this step's bias-grad partial (sum over batch) —
-            # the big gg2.sum(0) re-read disappears when every step fused
-            used = ext.lstm_pointwise_bwd(
-                grad_h.contiguous(), grad_out[ti], grad_c.contiguous(),
-                gates_all[ti], c_in.contiguous(),
-                mask[ti] if mask is not None else empty_mask,
-                grad_gates_all[ti], grad_c_prev, grad_h_pass,
-                bias_accum if bias_accum is not None else empty_mask,
-            )
-            bias_fused = bias_fused and bool(used)
-            gg_t = grad_gates_all[ti]
-            if use_rg_d and gg_t.stride(1) == 1 and gg_t.stride(0) % 8 == 0:
-                # stream order makes one buffer safe: this iteration's
-                # pointwise (the only reader of grad_h) completed first
-                ext.rec_gemm_dgrad(gg_t, w_hh_t_d, grad_h_pass, gh_buf)
-                grad_h = gh_buf
-            else:
-                # in place: an out-of-place addmm first copies its 2-D
-                # `self` into a fresh output (33 MB each way per step);
-                # the kernel's pass-through buffer becomes the next grad_h
-                # and the old grad_h the next pass-through target
-                grad_h_pass.addmm_(gg_t, w_hh)
-                grad_h, grad_h_pass = grad_h_pass, grad_h
-        else:
-            gg, gcp, ghp = _ref.lstm_pointwise_bwd_ref(
+    # each step(ti, c_in, grad_h, grad_c, spare_h, spare_c) returns the
+    # (grad_h, grad_c) flowing into the next (earlier-in-forward) step
+    if ext is None:
+        def step(ti, c_in, grad_h, grad_c, spare_h, spare_c):
+            gg, grad_c_prev, grad_h_pass = _ref.lstm_pointwise_bwd_ref(
                 grad_h + grad_out[ti], grad_c, gates_all[ti], c_in,
                 mask[ti] if mask is not None else None,
             )
             grad_gates_all[ti] = gg
-            grad_c_prev = gcp
-            grad_h_pass = ghp
-            grad_h = torch.mm(grad_gates_all[ti], w_hh) + grad_h_pass
-        grad_c, grad_c_prev = grad_c_prev, grad_c  # ping-pong buffers
-
-    # weight grads over all timesteps: the h input of step ti is the hidden
-    # history shifted by one step, whose bulk is a contiguous-rank slice of
-    # h_flat — two GEMMs (bulk + the h0 boundary row) instead of
-    # materialising a shifted copy of the whole history
-    gg2 = grad_gates_all.reshape(t_len * batch, gdim)
-    if t_len > 1:
-        if reverse:
-            bulk_gg = grad_gates_all[:-1].reshape((t_len - 1) * batch, gdim)
-            bulk_h = h_flat[batch:]
-            edge_gg = grad_gates_all[t_len - 1]
-        else:
-            bulk_gg = grad_gates_all[1:].reshape((t_len - 1) * batch, gdim)
-            bulk_h = h_flat[: (t_len - 1) * batch]
-            edge_gg = grad_gates_all[0]
-        grad_whh = torch.mm(bulk_gg.t(), bulk_h)
-        grad_whh = torch.addmm(grad_whh, edge_gg.t(), h0.to(dt))
+            return torch.mm(grad_gates_all[ti], w_hh) + grad_h_pass, grad_c_prev
     else:
-        grad_whh = torch.mm(gg2.t(), h0.to(dt))
-    grad_bias = (
-        bias_accum.sum(dim=0).to(dt)
-        if (bias_accum is not None and bias_fused)
-        else gg2.sum(dim=0)
+        empty_mask = torch.empty(0, device=dev)
+        if _mfma_eligible(dt, hdim, w_hh) and _rec_fused(infer=False):
+            # fused gate grads + in-launch grad_h GEMM (lstm_rec_fused.hip):
+            # grad_gates goes to HBM once, the addmm disappears.  A backward
+            # only follows a training forward, hence infer=False.
+            w_hh_t = w_hh.t().contiguous()
+
+            def step(ti, c_in, grad_h, grad_c, spare_h, spare_c):
+                ext.lstm_rec_bwd(
+                    grad_h.contiguous(), grad_out[ti], grad_c.contiguous(),
+                    gates_all[ti], c_in.contiguous(), w_hh_t,
+                    mask[ti] if mask is not None else empty_mask,
+                    grad_gates_all[ti], spare_c, spare_h,
+                )
+                return spare_h, spare_c
+        else:
+            # in-kernel bias-grad accumulation: every step's pointwise
+            # kernel adds its sum over rows of grad_gates into an f32 slab
+            # [P, 4H] (block p owns row p; register sums, plain stores, no
+            # atomics), so the four whole-history gg2.sum(0) re-reads per
+            # step disappear.  NERRF_FUSED_BIAS=0 keeps the separate
+            # reduction for A/B runs.
+            slab_on = os.environ.get("NERRF_FUSED_BIAS", "1") == "1"
+            slab = (
+                torch.zeros(_bias_slab_rows(batch, hdim, dt), gdim,
+                            device=dev, dtype=torch.float32)
+                if slab_on else empty_mask
+            )
+            slab_used = slab_on
+
+            def step(ti, c_in, grad_h, grad_c, spare_h, spare_c):
+                nonlocal slab_used
+                gg_t = grad_gates_all[ti]
+                # grad_out[ti] is folded inside the kernel (no separate
+                # add), and so is this step's bias-grad partial (sum over
+                # batch) — the big gg2.sum(0) re-read disappears when every
+                # step fused
+                used = ext.lstm_pointwise_bwd(
+                    grad_h.contiguous(), grad_out[ti], grad_c.contiguous(),
+                    gates_all[ti], c_in.contiguous(),
+                    mask[ti] if mask is not None else empty_mask,
+                    gg_t, spare_c, spare_h, slab,
+                )
+                slab_used = slab_used and bool(used)
+                # in place: an out-of-place addmm first copies its 2-D
+                # `self` into a fresh output (33 MB each way per step);
+                # the kernel's pass-through buffer becomes the next grad_h
+                # and the old grad_h the next pass-through target
+                spare_h.addmm_(gg_t, w_hh)
+                return spare_h, spare_c
+
+    # iterate in the opposite order of forward; the c input of step ti is
+    # the previous forward step's output (or c0 at the start)
+    steps = range(t_len) if reverse else range(t_len - 1, -1, -1)
+    first, prev = (t_len - 1, 1) if reverse else (0, -1)
+    for ti in steps:
+        c_in = c0 if ti == first else c_all[ti + prev]
+        new_h, new_c = step(ti, c_in, grad_h, grad_c, spare_h, spare_c)
+        spare_h, spare_c, grad_h, grad_c = grad_h, grad_c, new_h, new_c
+
+    grad_whh, grad_bias = _weight_grads(
+        grad_gates_all, h_flat, h0, reverse, slab if slab_used else None
     )
     return grad_gates_all, grad_h, grad_c, grad_whh, grad_bias
+
+
+def _infer_mode(*tensors) -> bool:
+    return not torch.is_grad_enabled() or not any(t.requires_grad for t in tensors)
+
+
+def _norm_mask(mask: Optional[torch.Tensor]) -> Optional[torch.Tensor]:
+    """[T, B] mask as the contiguous f32 constant the kernels read."""
+    return mask.detach().contiguous().to(torch.float32) if mask is not None else None
 
 
 class _LSTMSeqFn(torch.autograd.Function):
@@ -346,46 +329,73 @@ class _LSTMSeqFn(torch.autograd.Function):
         return grad_xg, grad_h0, grad_c0, grad_whh, grad_bias, None, None, None
 
 
-class _LSTMBiLayerFn(torch.autograd.Function):
-    """One bidirectional layer into a single [T, B, 2H] buffer."""
-
-    @staticmethod
-    def forward(ctx, xg_f, xg_b, h0, c0, w_f, b_f, w_b, b_b, mask, infer: bool = False):
-        t_len, batch, gdim = xg_f.shape
-        hdim = gdim // 4
-        h2 = torch.empty(t_len, batch, 2 * hdim, device=xg_f.device, dtype=xg_f.dtype)
-        ext = get_native(xg_f)
-        c_f, g_f = _dir_forward(
-            ext, xg_f, h0, c0, w_f, b_f, mask, False, infer, h2[:, :, :hdim]
-        )
+def _bi_forward(xg_f, xg_b, h0, c0, w_f, b_f, w_b, b_b, mask, infer,
+                overlap=False):
+    """Both directions of one layer into a single [T, B, 2H] buffer (fwd
+    cols 0:H, bwd H:2H).  Returns (h2, tensors to save for `_bi_backward`)."""
+    t_len, batch, gdim = xg_f.shape
+    hdim = gdim // 4
+    h2 = torch.empty(t_len, batch, 2 * hdim, device=xg_f.device, dtype=xg_f.dtype)
+    ext = get_native(xg_f)
+    if overlap:
+        main = torch.cuda.current_stream()
+        side = torch.cuda.Stream()
+        side.wait_stream(main)  # xg/h0/c0 ready
+    c_f, g_f = _dir_forward(
+        ext, xg_f, h0, c0, w_f, b_f, mask, False, infer, h2[:, :, :hdim]
+    )
+    with torch.cuda.stream(side) if overlap else contextlib.nullcontext():
         c_b, g_b = _dir_forward(
             ext, xg_b, h0, c0, w_b, b_b, mask, True, infer, h2[:, :, hdim:]
         )
-        ctx.save_for_backward(
-            g_f, g_b, h2, c_f, c_b, h0, c0, w_f, w_b,
-            mask if mask is not None else torch.empty(0, device=xg_f.device),
-        )
+    if overlap:
+        main.wait_stream(side)
+        # cross-stream allocator safety: h2 (allocated on main) was
+        # written on the side stream; c_b (allocated on side) is
+        # consumed/freed on main — record each tensor's FOREIGN stream
+        h2.record_stream(side)
+        c_b.record_stream(main)
+    return h2, (
+        g_f, g_b, h2, c_f, c_b, h0, c0, w_f, w_b,
+        mask if mask is not None else torch.empty(0, device=xg_f.device),
+    )
+
+
+def _bi_backward(saved, grad2, gg_f=None, gg_b=None):
+    """Backward of `_bi_forward`.  gg_f / gg_b: optional [T, B, 4H] targets
+    for the two directions' gate grads (see `_dir_backward`).  Returns
+    (grad_xg_f, grad_xg_b, grad_h0, grad_c0, grad_w_f, grad_b_f, grad_w_b,
+    grad_b_b)."""
+    g_f, g_b, h2, c_f, c_b, h0, c0, w_f, w_b, mask_t = saved
+    mask = mask_t if mask_t.numel() else None
+    t_len, batch, hdim2 = h2.shape
+    hdim = hdim2 // 2
+    ext = get_native(h2)
+    grad2 = grad2.contiguous()  # one [T, B, 2H] layout fix at most
+    h2_flat = h2.reshape(t_len * batch, hdim2)
+    gxf, gh0f, gc0f, gwf, gbf = _dir_backward(
+        ext, grad2[:, :, :hdim], g_f, h2_flat[:, :hdim], c_f, h0, c0,
+        w_f, mask, False, gg_out=gg_f,
+    )
+    gxb, gh0b, gc0b, gwb, gbb = _dir_backward(
+        ext, grad2[:, :, hdim:], g_b, h2_flat[:, hdim:], c_b, h0, c0,
+        w_b, mask, True, gg_out=gg_b,
+    )
+    return gxf, gxb, gh0f + gh0b, gc0f + gc0b, gwf, gbf, gwb, gbb
+
+
+class _LSTMBiLayerFn(torch.autograd.Function):
+    """One bidirectional layer from two [T, B, 4H] input projections."""
+
+    @staticmethod
+    def forward(ctx, xg_f, xg_b, h0, c0, w_f, b_f, w_b, b_b, mask, infer: bool = False):
+        h2, saved = _bi_forward(xg_f, xg_b, h0, c0, w_f, b_f, w_b, b_b, mask, infer)
+        ctx.save_for_backward(*saved)
         return h2
 
     @staticmethod
     def backward(ctx, grad2):
-        g_f, g_b, h2, c_f, c_b, h0, c0, w_f, w_b, mask_t = ctx.saved_tensors
-        mask = mask_t if mask_t.numel() else None
-        t_len, batch, hdim2 = h2.shape
-        hdim = hdim2 // 2
-        ext = get_native(h2)
-        grad2 = grad2.contiguous()  # one [T, B, 2H] layout fix at most
-        h2_flat = h2.reshape(t_len * batch, hdim2)
-        gxf, gh0f, gc0f, gwf, gbf = _dir_backward(
-            ext, grad2[:, :, :hdim], g_f, h2_flat[:, :hdim], c_f, h0, c0,
-            w_f, mask, False,
-        )
-        gxb, gh0b, gc0b, gwb, gbb = _dir_backward(
-            ext, grad2[:, :, hdim:], g_b, h2_flat[:, hdim:], c_b, h0, c0,
-            w_b, mask, True,
-        )
-        return (gxf, gxb, gh0f + gh0b, gc0f + gc0b, gwf, gbf, gwb, gbb,
-                None, None)
+        return (*_bi_backward(ctx.saved_tensors, grad2), None, None)
 
 
 class _LSTMBiLayer2Fn(torch.autograd.Function):
@@ -397,11 +407,7 @@ class _LSTMBiLayer2Fn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, xg2, h0, c0, w_f, b_f, w_b, b_b, mask, infer: bool = False):
-        t_len, batch, gdim2 = xg2.shape
-        gdim = gdim2 // 2
-        hdim = gdim // 4
-        h2 = torch.empty(t_len, batch, 2 * hdim, device=xg2.device, dtype=xg2.dtype)
-        ext = get_native(xg2)
+        gdim = xg2.shape[2] // 2
         # the two directions are independent recurrence chains; at inference
         # (no autograd stream bookkeeping) they can overlap on a side HIP
         # stream — each chain is 100 serial small-grid kernels, so the
@@ -412,62 +418,58 @@ class _LSTMBiLayer2Fn(torch.autograd.Function):
             and xg2.is_cuda
             and os.environ.get("NERRF_STREAM_DIRS", "0") == "1"
         )
-        if overlap:
-            main = torch.cuda.current_stream()
-            side = torch.cuda.Stream()
-            side.wait_stream(main)  # xg2/h0/c0 ready
-            c_f, g_f = _dir_forward(
-                ext, xg2[:, :, :gdim], h0, c0, w_f, b_f, mask, False, infer,
-                h2[:, :, :hdim]
-            )
-            with torch.cuda.stream(side):
-                c_b, g_b = _dir_forward(
-                    ext, xg2[:, :, gdim:], h0, c0, w_b, b_b, mask, True, infer,
-                    h2[:, :, hdim:]
-                )
-            main.wait_stream(side)
-            # cross-stream allocator safety: h2 (allocated on main) was
-            # written on the side stream; c_b (allocated on side) is
-            # consumed/freed on main — record each tensor's FOREIGN stream
-            h2.record_stream(side)
-            c_b.record_stream(main)
-        else:
-            c_f, g_f = _dir_forward(
-                ext, xg2[:, :, :gdim], h0, c0, w_f, b_f, mask, False, infer,
-                h2[:, :, :hdim]
-            )
-            c_b, g_b = _dir_forward(
-                ext, xg2[:, :, gdim:], h0, c0, w_b, b_b, mask, True, infer,
-                h2[:, :, hdim:]
-            )
-        ctx.save_for_backward(
-            g_f, g_b, h2, c_f, c_b, h0, c0, w_f, w_b,
-            mask if mask is not None else torch.empty(0, device=xg2.device),
+        h2, saved = _bi_forward(
+            xg2[:, :, :gdim], xg2[:, :, gdim:], h0, c0, w_f, b_f, w_b, b_b,
+            mask, infer, overlap,
         )
+        ctx.save_for_backward(*saved)
         return h2
 
     @staticmethod
     def backward(ctx, grad2):
-        g_f, g_b, h2, c_f, c_b, h0, c0, w_f, w_b, mask_t = ctx.saved_tensors
-        mask = mask_t if mask_t.numel() else None
+        h2 = ctx.saved_tensors[2]
         t_len, batch, hdim2 = h2.shape
-        hdim = hdim2 // 2
-        gdim = 4 * hdim
-        ext = get_native(h2)
-        grad2 = grad2.contiguous()
-        h2_flat = h2.reshape(t_len * batch, hdim2)
+        gdim = 2 * hdim2  # 4H
         grad_xg2 = torch.empty(t_len, batch, 2 * gdim, device=h2.device,
                                dtype=h2.dtype)
-        _, gh0f, gc0f, gwf, gbf = _dir_backward(
-            ext, grad2[:, :, :hdim], g_f, h2_flat[:, :hdim], c_f, h0, c0,
-            w_f, mask, False, gg_out=grad_xg2[:, :, :gdim],
+        grads = _bi_backward(
+            ctx.saved_tensors, grad2, grad_xg2[:, :, :gdim], grad_xg2[:, :, gdim:]
         )
-        _, gh0b, gc0b, gwb, gbb = _dir_backward(
-            ext, grad2[:, :, hdim:], g_b, h2_flat[:, hdim:], c_b, h0, c0,
-            w_b, mask, True, gg_out=grad_xg2[:, :, gdim:],
-        )
-        return (grad_xg2, gh0f + gh0b, gc0f + gc0b, gwf, gbf, gwb, gbb,
-                None, None)
+        return (grad_xg2, *grads[2:], None, None)
+
+
+def lstm_sequence(
+    xg: torch.Tensor,  # [T, B, 4H]
+    h0: torch.Tensor,
+    c0: torch.Tensor,
+    w_hh: torch.Tensor,
+    bias: torch.Tensor,
+    mask: Optional[torch.Tensor] = None,  # [T, B]
+    reverse: bool = False,
+) -> torch.Tensor:
+    infer = _infer_mode(xg, h0, c0, w_hh, bias)
+    return _LSTMSeqFn.apply(
+        xg.contiguous(), h0, c0, w_hh, bias, _norm_mask(mask), reverse, infer
+    )
+
+
+def lstm_bilayer(
+    xg_f: torch.Tensor,  # [T, B, 4H] forward-direction input projection
+    xg_b: torch.Tensor,  # [T, B, 4H] backward-direction input projection
+    h0: torch.Tensor,
+    c0: torch.Tensor,
+    w_f: torch.Tensor,
+    b_f: torch.Tensor,
+    w_b: torch.Tensor,
+    b_b: torch.Tensor,
+    mask: Optional[torch.Tensor] = None,  # [T, B]
+) -> torch.Tensor:
+    """Both directions of one layer -> [T, B, 2H] (fwd cols 0:H, bwd H:2H)."""
+    infer = _infer_mode(xg_f, xg_b, h0, c0, w_f, b_f, w_b, b_b)
+    return _LSTMBiLayerFn.apply(
+        xg_f.contiguous(), xg_b.contiguous(), h0, c0, w_f, b_f, w_b, b_b,
+        _norm_mask(mask), infer,
+    )
 
 
 def lstm_bilayer2(
@@ -483,44 +485,8 @@ def lstm_bilayer2(
     """Both directions of one layer from a single concatenated projection
     -> [T, B, 2H].  Rows of xg2 must be contiguous (the tensor itself may
     be a reshaped GEMM output)."""
-    m = mask.detach().contiguous().to(torch.float32) if mask is not None else None
     infer = _infer_mode(xg2, h0, c0, w_f, b_f, w_b, b_b)
     assert xg2.stride(2) == 1, "xg2 rows must be contiguous"
-    return _LSTMBiLayer2Fn.apply(xg2, h0, c0, w_f, b_f, w_b, b_b, m, infer)
-
-
-def _infer_mode(*tensors) -> bool:
-    return not torch.is_grad_enabled() or not any(t.requires_grad for t in tensors)
-
-
-def lstm_sequence(
-    xg: torch.Tensor,  # [T, B, 4H]
-    h0: torch.Tensor,
-    c0: torch.Tensor,
-    w_hh: torch.Tensor,
-    bias: torch.Tensor,
-    mask: Optional[torch.Tensor] = None,  # [T, B]
-    reverse: bool = False,
-) -> torch.Tensor:
-    m = mask.detach().contiguous().to(torch.float32) if mask is not None else None
-    infer = _infer_mode(xg, h0, c0, w_hh, bias)
-    return _LSTMSeqFn.apply(xg.contiguous(), h0, c0, w_hh, bias, m, reverse, infer)
-
-
-def lstm_bilayer(
-    xg_f: torch.Tensor,  # [T, B, 4H] forward-direction input projection
-    xg_b: torch.Tensor,  # [T, B, 4H] backward-direction input projection
-    h0: torch.Tensor,
-    c0: torch.Tensor,
-    w_f: torch.Tensor,
-    b_f: torch.Tensor,
-    w_b: torch.Tensor,
-    b_b: torch.Tensor,
-    mask: Optional[torch.Tensor] = None,  # [T, B]
-) -> torch.Tensor:
-    """Both directions of one layer -> [T, B, 2H] (fwd cols 0:H, bwd H:2H)."""
-    m = mask.detach().contiguous().to(torch.float32) if mask is not None else None
-    infer = _infer_mode(xg_f, xg_b, h0, c0, w_f, b_f, w_b, b_b)
-    return _LSTMBiLayerFn.apply(
-        xg_f.contiguous(), xg_b.contiguous(), h0, c0, w_f, b_f, w_b, b_b, m, infer
+    return _LSTMBiLayer2Fn.apply(
+        xg2, h0, c0, w_f, b_f, w_b, b_b, _norm_mask(mask), infer
     )

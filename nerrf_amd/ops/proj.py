@@ -45,7 +45,7 @@ class _DualProjFn(torch.autograd.Function):
     def forward(ctx, x, w_f, w_b):
         ext = get_native(x)
         ctx.save_for_backward(x, w_f, w_b)
-        if ext is not None and hasattr(ext, "proj_fwd_dual") and _use_stream(x, w_f, w_b):
+        if ext is not None and _use_stream(x, w_f, w_b):
             m = x.shape[0]
             c1 = torch.empty(m, 1024, device=x.device, dtype=x.dtype)
             c2 = torch.empty(m, 1024, device=x.device, dtype=x.dtype)
@@ -61,11 +61,7 @@ class _DualProjFn(torch.autograd.Function):
         g2 = g2.contiguous()
         gx = None
         if ctx.needs_input_grad[0]:
-            if (
-                ext is not None
-                and hasattr(ext, "proj_dgrad_dual")
-                and _use_stream(x, w_f, w_b)
-            ):
+            if ext is not None and _use_stream(x, w_f, w_b):
                 gx = torch.empty_like(x)
                 ext.proj_dgrad_dual(
                     g1, g2, w_f.t().contiguous(), w_b.t().contiguous(), gx
@@ -76,7 +72,6 @@ class _DualProjFn(torch.autograd.Function):
         if ctx.needs_input_grad[1] or ctx.needs_input_grad[2]:
             if (
                 ext is not None
-                and hasattr(ext, "proj_wgrad")
                 and _use_stream(x, w_f, w_b)
                 and os.environ.get("NERRF_STREAM_WGRAD", "1") == "1"
             ):

@@ -303,8 +303,9 @@ def test_lstm_step_fused_full_matches_reference(gpu_device):
     assert torch.allclose(gates.float().cpu(), g_ref, atol=5e-2, rtol=5e-2)
 
 
-def test_lstm_sequence_bf16_fused_path(gpu_device):
-    """bf16 lstm_sequence (fused MFMA step path) vs fp32 CPU loop."""
+def test_lstm_sequence_bf16_default_path(gpu_device):
+    """bf16 lstm_sequence on the default path (no flag set; no input requires
+    grad, so H=256 takes the default inference step) vs fp32 CPU loop."""
     from nerrf_amd.ops import lstm_sequence
     from nerrf_amd.ops.reference import lstm_pointwise_fwd_ref
 
@@ -931,6 +932,46 @@ def test_lstm_bilayer2_matches_bilayer(gpu_device):
     for a, c, name in ((wf.grad, wf2.grad, "wf"), (wb.grad, wb2.grad, "wb"),
                        (bf.grad, bf2.grad, "bf"), (bb.grad, bb2.grad, "bb")):
         assert torch.allclose(a.float(), c.float(), atol=1e-5), name
+
+
+def test_lstm_bilayer2_inference_matches_cpu_reference(gpu_device):
+    """The serving hot path: lstm_bilayer2 under no_grad with default flags
+    (fused recurrent step, null gates pointer, xg slabs of row stride 2*4H,
+    h slabs of row stride 2H) vs the fp32 CPU loop per direction.  B is a
+    multiple of neither 64 nor 128; lengths include 1 and T; h0/c0 non-zero.
+    Tolerance: that of test_lstm_rec_fused_fwd_matches_split_and_ref, the
+    same kernel against the same reference at the same T."""
+    from nerrf_amd.ops.lstm_seq import lstm_bilayer2
+
+    torch.manual_seed(47)
+    t, b, hd = 5, 130, 256
+    gd = 4 * hd
+    dt = torch.bfloat16
+    xg2 = (torch.randn(t, b, 2 * gd, device=gpu_device) * 0.5).to(dt)
+    h0 = (torch.randn(b, hd, device=gpu_device) * 0.5).to(dt)
+    c0 = (torch.randn(b, hd, device=gpu_device) * 0.5).to(dt)
+    w_f = (torch.randn(gd, hd, device=gpu_device) * 0.05).to(dt)
+    w_b = (torch.randn(gd, hd, device=gpu_device) * 0.05).to(dt)
+    b_f = torch.randn(gd, device=gpu_device).to(dt)
+    b_b = torch.randn(gd, device=gpu_device).to(dt)
+    lengths = torch.randint(1, t + 1, (b,), device=gpu_device)
+    lengths[0], lengths[1] = 1, t
+    mask = (torch.arange(t, device=gpu_device).unsqueeze(1)
+            < lengths.unsqueeze(0)).float()  # [T, B]
+
+    with torch.no_grad():
+        out = lstm_bilayer2(xg2, h0, c0, w_f, b_f, w_b, b_b, mask)
+    ref_out = torch.cat(
+        [
+            _lstm_cpu_ref_seq(xg2[:, :, :gd], h0, c0, w_f, b_f, mask, False),
+            _lstm_cpu_ref_seq(xg2[:, :, gd:], h0, c0, w_b, b_b, mask, True),
+        ],
+        dim=-1,
+    )
+    assert out.shape == (t, b, 2 * hd)
+    assert torch.allclose(out.float().cpu(), ref_out, atol=6e-2, rtol=6e-2), (
+        f"max diff {(out.float().cpu() - ref_out).abs().max()}"
+    )
 
 
 def test_engine_device_delta_ring_matches_host_path(gpu_device):
