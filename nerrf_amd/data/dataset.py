@@ -6,7 +6,7 @@ CPU (numpy) and staged to the device as a handful of contiguous copies.
 """
 from __future__ import annotations
 
-from dataclasses import dataclass
+from dataclasses import dataclass, field
 from typing import Dict, Iterator, List, Optional
 
 import numpy as np
@@ -14,6 +14,7 @@ import torch
 
 from ..graph.constructor import build_graph, sliding_windows
 from ..graph.sampling import edge_reverse_index, reverse_index, sample_fanout, to_csr
+from ..ops.lstm_seq import SeqPlan, build_seq_plan
 from .labels import event_labels
 from .sequences import build_sequences
 from .synth import AttackWindow, SynthConfig, generate
@@ -42,6 +43,14 @@ class WindowBatch:
     rev_w: Optional[np.ndarray] = None
     e0_rev: Optional[tuple] = None  # edge endpoint reverse (dst, src, w)
     e1_rev: Optional[tuple] = None
+    _seq_plan: Optional[SeqPlan] = field(default=None, repr=False, compare=False)
+
+    def seq_plan(self) -> SeqPlan:
+        """The sequences' length-sort plan on the CPU, built once per batch
+        (every epoch stages the same batch again)."""
+        if self._seq_plan is None:
+            self._seq_plan = build_seq_plan(self.seq_lengths, self.seq_feats.shape[1])
+        return self._seq_plan
 
     def to_torch(self, device="cpu", dtype=torch.float32) -> Dict[str, torch.Tensor]:
         def t(a, dt=None):
@@ -61,6 +70,9 @@ class WindowBatch:
             "y_edge": t(self.y_edge, torch.float32),
             "seq_feats": t(self.seq_feats, dtype),
             "seq_lengths": t(self.seq_lengths),
+            # length-sort plan of the packed BiLSTM, from the numpy lengths
+            # already at hand: no device-to-host copy in the training step
+            "seq_plan": self.seq_plan().to(device),
             "y_seq": t(self.y_seq, torch.float32),
             "n_events": torch.tensor(self.n_events),
             "nbr_rev": None

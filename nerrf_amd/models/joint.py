@@ -41,7 +41,7 @@ class NerrfJointModel(nn.Module):
 
     def forward(self, batch: Dict[str, torch.Tensor]):
         """batch keys: x, nbr_idx, nbr_w, edge_index, edge_weight, edge_ts,
-        seq_feats, seq_lengths (+ optional y_node, y_edge, y_seq)."""
+        seq_feats, seq_lengths (+ optional seq_plan, y_node, y_edge, y_seq)."""
         node_logit, edge_logit = self.gnn(
             batch["x"],
             batch["nbr_idx"],
@@ -54,7 +54,12 @@ class NerrfJointModel(nn.Module):
         )
         seq_logit = None
         if batch.get("seq_feats") is not None and batch["seq_feats"].shape[0] > 0:
-            seq_logit = self.lstm(batch["seq_feats"], batch["seq_lengths"])
+            # seq_plan (optional): the host-built length-sort plan of
+            # seq_lengths (WindowBatch.to_torch) — the packed BiLSTM then
+            # needs no device-to-host copy and the step stays capturable
+            seq_logit = self.lstm(
+                batch["seq_feats"], batch["seq_lengths"], batch.get("seq_plan")
+            )
         return node_logit, edge_logit, seq_logit
 
     def loss(

@@ -7,19 +7,33 @@ MI355X-first structure: the input projection for ALL timesteps is one large
 GEMM (hipBLASLt via torch.matmul — a plain library GEMM), and the
 recurrence of a whole layer, both directions, goes through
 `nerrf_amd.ops.lstm_seq.lstm_bilayer2`, the sequence op backed by the
-hand-written CDNA4 HIP step kernels on GPU.  Variable lengths are handled
-with masked state updates so the whole batch stays dense — no
-PackedSequence host logic.
+hand-written CDNA4 HIP step kernels on GPU.
+
+Variable lengths.  Training (gradients needed) packs the batch to its live
+rows: sequences are sorted by length once per batch (`SeqPlan`, built on the
+host with the batch or from `lengths`), every LSTM tensor holds only the
+sum(lengths) live (timestep, sequence) rows, and the recurrence runs
+max(lengths) steps through `lstm_bilayer2_packed`.  NERRF_LSTM_PACKED=0
+(docs/flags.md) selects the dense path there too.  Inference keeps the whole
+batch dense with masked state updates (`lstm_bilayer2`, the rec-fused step
+kernel).
 """
 from __future__ import annotations
 
+import os
 from dataclasses import dataclass
+from typing import Optional
 
 import torch
 import torch.nn as nn
 
 from ..ops import lstm_sequence
-from ..ops.lstm_seq import lstm_bilayer2
+from ..ops.lstm_seq import (
+    SeqPlan,
+    build_seq_plan,
+    lstm_bilayer2,
+    lstm_bilayer2_packed,
+)
 
 
 @dataclass
@@ -79,8 +93,56 @@ class BiLSTMDetector(nn.Module):
         self.dirs = nn.ModuleList(dirs)
         self.head = nn.Linear(2 * c.hidden, 1)
 
-    def forward(self, feats: torch.Tensor, lengths: torch.Tensor) -> torch.Tensor:
-        """feats: [B, T, E]; lengths: [B] -> per-sequence logit [B]."""
+    def forward(
+        self,
+        feats: torch.Tensor,
+        lengths: torch.Tensor,
+        plan: Optional[SeqPlan] = None,
+    ) -> torch.Tensor:
+        """feats: [B, T, E]; lengths: [B] -> per-sequence logit [B].
+
+        `plan` (optional): the `SeqPlan` of `lengths`, e.g. the one
+        `WindowBatch.to_torch` builds on the host; without it the packed
+        path builds one from `lengths` with one device-to-host copy."""
+        packed = (
+            os.environ.get("NERRF_LSTM_PACKED", "1") == "1"
+            and torch.is_grad_enabled()
+            and any(p.requires_grad for p in self.parameters())
+        )
+        if packed:
+            return self._forward_packed(feats, lengths, plan)
+        return self._forward_dense(feats, lengths)
+
+    def _forward_packed(self, feats, lengths, plan) -> torch.Tensor:
+        """Training path: only the sum(lengths) live (timestep, sequence)
+        rows exist; sequences are sorted by length and every layer runs on
+        packed time-major tensors (ops/lstm_seq.py, `SeqPlan`)."""
+        b, t, e = feats.shape
+        hid = self.cfg.hidden
+        if plan is None:
+            plan = build_seq_plan(lengths, t, feats.device)
+        assert plan.n_seq == b and plan.t_max == t, "plan does not match feats"
+        n = plan.n_rows
+        if n == 0:  # every sequence is empty: zero final states
+            return self.head(feats.new_zeros(b, 2 * hid)).squeeze(-1)
+        h = feats.reshape(b * t, e).index_select(0, plan.pack_idx)  # [N, E]
+        for layer in self.dirs:
+            f, r = layer[0], layer[1]
+            w_cat = torch.cat([f.w_ih, r.w_ih], dim=0)  # [2*4H, K]
+            xg2p = torch.matmul(h, w_cat.t())  # [N, 2*4H], one GEMM
+            h = lstm_bilayer2_packed(xg2p, plan, f.w_hh, f.b, r.w_hh, r.b)
+        # forward state of sorted row r at t = len-1, backward state at t = 0,
+        # gathered in the original sequence order.  The indices are unique
+        # (but for length-0 sequences, zeroed below), so the backward is an
+        # index_add_ and not the sort-based indexing backward.
+        fin = h.reshape(2 * n, hid).index_select(0, plan.fin_idx).view(b, 2 * hid)
+        if plan.has_empty:
+            fin = fin * plan.live.to(fin.dtype)
+        return self.head(fin).squeeze(-1)
+
+    def _forward_dense(self, feats: torch.Tensor, lengths: torch.Tensor) -> torch.Tensor:
+        """Dense masked path over all B x T positions: inference (the
+        rec-fused step kernel) and NERRF_LSTM_PACKED=0."""
         b, t, _ = feats.shape
         ar = torch.arange(t, device=feats.device)
         mask = (ar.unsqueeze(1) < lengths.unsqueeze(0)).to(feats.dtype)  # [T, B]

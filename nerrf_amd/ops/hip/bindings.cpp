@@ -26,11 +26,11 @@ void launch_gather_mean_bwd_csr(const void*, const long*, const long*,
 void launch_lstm_pointwise_fwd(const void*, const void*, const void*,
                                const void*, const void*, const float*, void*,
                                void*, void*, long, int, long, long, long,
-                               bool, hipStream_t);
+                               long, bool, hipStream_t);
 bool launch_lstm_pointwise_bwd(const void*, const void*, const void*,
                                const void*, const void*, const float*, void*,
                                void*, void*, float*, long, long, int, long,
-                               long, bool, hipStream_t);
+                               long, long, long, bool, hipStream_t);
 void launch_lstm_step_fused(const void*, const void*, const void*, const void*,
                             const void*, const float*, void*, void*, void*,
                             int, bool, hipStream_t);
@@ -150,12 +150,26 @@ torch::Tensor gather_mean_bwd_csr(torch::Tensor grad_out,
   return ws.to(grad_out.scalar_type());
 }
 
+// The vectorised pointwise kernels move 16 bytes per access.  Row strides
+// that are multiples of the vector width are not enough: a tensor that is a
+// row slice of a packed buffer starts at a row offset, so its base address
+// is checked too.
+void check_vec_base(const torch::Tensor& t, bool vec, const char* name) {
+  TORCH_CHECK(!vec || t.numel() == 0 ||
+                  reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0,
+              name, " must start on a 16-byte boundary");
+}
+
 // Writes into caller-provided (h_out, c_out, gates_act) so the sequence loop
 // can target time-major buffers directly (no per-step allocation or copy).
+// The step covers h_out.size(0) rows.  prev_rows (< 0: all rows) is how many
+// of them have a previous state: hg, c_prev and h_prev need only that many
+// rows, and rows beyond start from zero without reading any of the three.
 void lstm_pointwise_fwd(torch::Tensor hg, torch::Tensor xg, torch::Tensor bias,
                         torch::Tensor c_prev, torch::Tensor h_prev,
                         torch::Tensor mask, torch::Tensor h_out,
-                        torch::Tensor c_out, torch::Tensor gates_act) {
+                        torch::Tensor c_out, torch::Tensor gates_act,
+                        long prev_rows) {
   check_gpu_contig(hg, "hg");
   const long xg_stride = row_stride_checked(xg, "xg");
   check_gpu_contig(c_prev, "c_prev");
@@ -164,10 +178,20 @@ void lstm_pointwise_fwd(torch::Tensor hg, torch::Tensor xg, torch::Tensor bias,
   check_gpu_contig(c_out, "c_out");
   const bool want_gates = gates_act.numel() > 0;
   if (want_gates) check_gpu_contig(gates_act, "gates_act");
-  const long batch = c_prev.size(0);
-  const int hdim = c_prev.size(1);
+  const long batch = c_out.size(0);
+  const int hdim = c_out.size(1);
+  if (prev_rows < 0) prev_rows = batch;
+  TORCH_CHECK(prev_rows <= batch, "prev_rows exceeds the step's rows");
+  TORCH_CHECK(hg.dim() == 2 && c_prev.dim() == 2 && hg.size(0) >= prev_rows &&
+                  c_prev.size(0) >= prev_rows && h_prev.size(0) >= prev_rows &&
+                  c_prev.size(1) == hdim && h_prev.size(1) == hdim,
+              "hg/c_prev/h_prev must cover prev_rows rows");
   TORCH_CHECK(hg.size(1) == 4 * hdim && xg.size(1) == 4 * hdim,
               "hg/xg must be [B, 4H]");
+  TORCH_CHECK(xg.size(0) == batch && h_out.size(0) == batch &&
+                  h_out.size(1) == hdim &&
+                  (!want_gates || gates_act.size(0) == batch),
+              "xg/h_out/c_out/gates_act must have the step's rows");
   TORCH_CHECK(bias.numel() == 4 * hdim, "bias must be [4H]");
   const float* mask_ptr = nullptr;
   torch::Tensor mf;
@@ -178,12 +202,24 @@ void lstm_pointwise_fwd(torch::Tensor hg, torch::Tensor xg, torch::Tensor bias,
     mask_ptr = mf.data_ptr<float>();
   }
   auto bc = bias.contiguous();
+  const bool bf16 = is_bf16(hg);
+  const int v = bf16 ? 8 : 4;
+  const bool vec = hdim % v == 0 && xg_stride % v == 0 &&
+                   hout_stride % v == 0 && hprev_stride % v == 0;
+  check_vec_base(hg, vec, "hg");
+  check_vec_base(xg, vec, "xg");
+  check_vec_base(bc, vec, "bias");
+  check_vec_base(c_prev, vec, "c_prev");
+  check_vec_base(h_prev, vec, "h_prev");
+  check_vec_base(h_out, vec, "h_out");
+  check_vec_base(c_out, vec, "c_out");
+  check_vec_base(gates_act, vec, "gates_act");
   auto stream = at::hip::getCurrentHIPStream();
   nerrf::launch_lstm_pointwise_fwd(
       hg.data_ptr(), xg.data_ptr(), bc.data_ptr(), c_prev.data_ptr(),
       h_prev.data_ptr(), mask_ptr, h_out.data_ptr(), c_out.data_ptr(),
       want_gates ? gates_act.data_ptr() : nullptr, batch, hdim, xg_stride,
-      hout_stride, hprev_stride, is_bf16(hg), stream.stream());
+      hout_stride, hprev_stride, prev_rows, bf16, stream.stream());
 }
 
 // grad_out_t (may be empty): this timestep's dL/dh, folded in-kernel so the
@@ -197,31 +233,60 @@ void lstm_pointwise_fwd(torch::Tensor hg, torch::Tensor xg, torch::Tensor bias,
 // fused accumulation ran: it needs the vectorised path and
 // 256 % (H/V) == 0 (V = 8 for bf16, 4 for f32); otherwise the slab is left
 // untouched and false is returned.
+// The step covers gates_act.size(0) rows.  in_rows (< 0: all rows): rows
+// with an incoming recurrent gradient — grad_h and grad_c need only that
+// many rows and the rest take 0 without a read.  prev_rows (< 0: all rows):
+// rows whose previous cell state exists; c_prev needs only that many.
+// grad_h_pass may be empty when there is no mask (it is identically zero
+// then): the store is skipped.
 bool lstm_pointwise_bwd(torch::Tensor grad_h, torch::Tensor grad_out_t,
                         torch::Tensor grad_c, torch::Tensor gates_act,
                         torch::Tensor c_prev, torch::Tensor mask,
                         torch::Tensor grad_gates, torch::Tensor grad_c_prev,
-                        torch::Tensor grad_h_pass, torch::Tensor bias_accum) {
+                        torch::Tensor grad_h_pass, torch::Tensor bias_accum,
+                        long in_rows, long prev_rows) {
   check_gpu_contig(grad_h, "grad_h");
   check_gpu_contig(grad_c, "grad_c");
   check_gpu_contig(gates_act, "gates_act");
   check_gpu_contig(c_prev, "c_prev");
   const long gg_stride = row_stride_checked(grad_gates, "grad_gates");
   check_gpu_contig(grad_c_prev, "grad_c_prev");
-  check_gpu_contig(grad_h_pass, "grad_h_pass");
-  const long batch = c_prev.size(0);
-  const int hdim = c_prev.size(1);
+  const bool want_pass = grad_h_pass.numel() > 0;
+  if (want_pass) check_gpu_contig(grad_h_pass, "grad_h_pass");
+  TORCH_CHECK(gates_act.dim() == 2 && gates_act.size(1) % 4 == 0,
+              "gates_act must be [B, 4H]");
+  const long batch = gates_act.size(0);
+  const int hdim = gates_act.size(1) / 4;
+  if (in_rows < 0) in_rows = batch;
+  if (prev_rows < 0) prev_rows = batch;
+  TORCH_CHECK(in_rows <= batch && prev_rows <= batch,
+              "in_rows/prev_rows exceed the step's rows");
+  TORCH_CHECK(grad_h.numel() >= in_rows * hdim && grad_c.numel() >= in_rows * hdim,
+              "grad_h/grad_c must cover in_rows rows");
+  TORCH_CHECK(c_prev.numel() >= prev_rows * hdim,
+              "c_prev must cover prev_rows rows");
+  TORCH_CHECK(grad_gates.size(0) == batch && grad_gates.size(1) == 4 * hdim &&
+                  grad_c_prev.numel() >= batch * hdim &&
+                  (!want_pass || grad_h_pass.numel() >= batch * hdim),
+              "grad_gates/grad_c_prev/grad_h_pass must have the step's rows");
+  TORCH_CHECK(want_pass || mask.numel() == 0,
+              "grad_h_pass is required with a mask");
   const float* mask_ptr = nullptr;
   torch::Tensor mf;
   if (mask.numel() > 0) {
     mf = mask.scalar_type() == torch::kFloat32 ? mask.contiguous()
                                                : mask.to(torch::kFloat32).contiguous();
+    TORCH_CHECK(mf.numel() == batch, "mask must be [B]");
     mask_ptr = mf.data_ptr<float>();
   }
   auto stream = at::hip::getCurrentHIPStream();
   const void* got = grad_out_t.numel() ? grad_out_t.data_ptr() : nullptr;
   long gout_stride = hdim;
-  if (grad_out_t.numel()) gout_stride = row_stride_checked(grad_out_t, "grad_out_t");
+  if (grad_out_t.numel()) {
+    gout_stride = row_stride_checked(grad_out_t, "grad_out_t");
+    TORCH_CHECK(grad_out_t.size(0) == batch && grad_out_t.size(1) == hdim,
+                "grad_out_t must be [B, H]");
+  }
   float* bias_ptr = nullptr;
   long accum_rows = 0;
   if (bias_accum.numel() > 0) {
@@ -232,11 +297,23 @@ bool lstm_pointwise_bwd(torch::Tensor grad_h, torch::Tensor grad_out_t,
     bias_ptr = bias_accum.data_ptr<float>();
     accum_rows = bias_accum.numel() / (4 * (long)hdim);
   }
+  const bool bf16 = is_bf16(grad_h);
+  const int v = bf16 ? 8 : 4;
+  const bool vec = hdim % v == 0 && gout_stride % v == 0 && gg_stride % v == 0;
+  check_vec_base(grad_h, vec, "grad_h");
+  check_vec_base(grad_out_t, vec, "grad_out_t");
+  check_vec_base(grad_c, vec, "grad_c");
+  check_vec_base(gates_act, vec, "gates_act");
+  check_vec_base(c_prev, vec, "c_prev");
+  check_vec_base(grad_gates, vec, "grad_gates");
+  check_vec_base(grad_c_prev, vec, "grad_c_prev");
+  check_vec_base(grad_h_pass, vec, "grad_h_pass");
   return nerrf::launch_lstm_pointwise_bwd(
       grad_h.data_ptr(), got, grad_c.data_ptr(), gates_act.data_ptr(),
       c_prev.data_ptr(), mask_ptr, grad_gates.data_ptr(),
-      grad_c_prev.data_ptr(), grad_h_pass.data_ptr(), bias_ptr, accum_rows,
-      batch, hdim, gout_stride, gg_stride, is_bf16(grad_h), stream.stream());
+      grad_c_prev.data_ptr(), want_pass ? grad_h_pass.data_ptr() : nullptr,
+      bias_ptr, accum_rows, batch, hdim, gout_stride, gg_stride, in_rows,
+      prev_rows, bf16, stream.stream());
 }
 
 // Fused recurrent step (bf16, H == 256): h_prev @ W_hh^T + LSTM pointwise
@@ -363,6 +440,8 @@ void rec_gemm_fwd(torch::Tensor a, torch::Tensor w, torch::Tensor c) {
               "rec_gemm_fwd requires [M,256] x [1024,256] -> [M,1024]");
   TORCH_CHECK(a_stride % 8 == 0 && c_stride % 8 == 0,
               "rec_gemm_fwd needs 16-B aligned rows");
+  check_vec_base(a, true, "a");
+  check_vec_base(c, true, "c");
   auto stream = at::hip::getCurrentHIPStream();
   nerrf::launch_rec_gemm_fwd(a.data_ptr(), w.data_ptr(), c.data_ptr(),
                              a.size(0), a_stride, c_stride, stream.stream());
@@ -797,7 +876,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("gather_mean_bwd", &gather_mean_bwd, "gather-mean backward");
   m.def("gather_mean_bwd_csr", &gather_mean_bwd_csr,
         "deterministic gather-mean backward over reverse CSR");
-  m.def("lstm_pointwise_fwd", &lstm_pointwise_fwd, "fused LSTM gate pointwise fwd");
+  m.def("lstm_pointwise_fwd", &lstm_pointwise_fwd,
+        "fused LSTM gate pointwise fwd", py::arg("hg"), py::arg("xg"),
+        py::arg("bias"), py::arg("c_prev"), py::arg("h_prev"), py::arg("mask"),
+        py::arg("h_out"), py::arg("c_out"), py::arg("gates_act"),
+        py::arg("prev_rows") = -1);
   m.def("lstm_rec_fwd", &lstm_rec_fwd,
         "fused recurrent GEMM + LSTM pointwise fwd (bf16, H=256)");
   m.def("lstm_rec_bwd", &lstm_rec_bwd,
@@ -813,5 +896,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("proj_wgrad", &proj_wgrad,
         "dual-direction input-projection weight grads (f32 partials)");
   m.def("lstm_step_fused", &lstm_step_fused, "fully-fused MFMA LSTM step (bf16, H=256)");
-  m.def("lstm_pointwise_bwd", &lstm_pointwise_bwd, "fused LSTM gate pointwise bwd");
+  m.def("lstm_pointwise_bwd", &lstm_pointwise_bwd,
+        "fused LSTM gate pointwise bwd", py::arg("grad_h"),
+        py::arg("grad_out_t"), py::arg("grad_c"), py::arg("gates_act"),
+        py::arg("c_prev"), py::arg("mask"), py::arg("grad_gates"),
+        py::arg("grad_c_prev"), py::arg("grad_h_pass"), py::arg("bias_accum"),
+        py::arg("in_rows") = -1, py::arg("prev_rows") = -1);
 }

@@ -20,6 +20,11 @@ namespace nerrf {
 // read gate slabs straight out of a [T, B, 2*4H] dual-direction projection.
 // hout_stride: row stride of h_out — lets both directions write straight
 // into the [T, B, 2H] concatenated output (no torch.cat afterwards).
+// prev_rows: rows of the previous state (hg, c_prev, h_prev).  Rows
+// b >= prev_rows start from a zero state (hg = c_prev = h_prev = 0) and read
+// none of the three — the packed sequence op runs a step over more rows than
+// its predecessor had (reverse direction) without a zero-fill or cat, and
+// the hg scratch may hold stale rows of a longer step there.
 template <typename T>
 __global__ void lstm_pointwise_fwd_kernel(
     const T* __restrict__ hg,         // [B, 4H] = h_prev @ W_hh^T (beta=0 GEMM)
@@ -32,7 +37,7 @@ __global__ void lstm_pointwise_fwd_kernel(
     T* __restrict__ c_out,            // [B, H]
     T* __restrict__ gates_act,        // [B, 4H] or nullptr (inference)
     long batch, int hdim, long xg_stride, long hout_stride,
-    long hprev_stride) {
+    long hprev_stride, long prev_rows) {
   const long total = batch * hdim;
   for (long t = blockIdx.x * (long)blockDim.x + threadIdx.x; t < total;
        t += (long)gridDim.x * blockDim.x) {
@@ -40,21 +45,30 @@ __global__ void lstm_pointwise_fwd_kernel(
     const int d = (int)(t % hdim);
     const long g0 = b * 4 * hdim + d;
     const long x0 = b * xg_stride + d;
-    const float ip = to_f32(hg[g0]) + to_f32(xg[x0]) + to_f32(bias[d]);
-    const float fp = to_f32(hg[g0 + hdim]) + to_f32(xg[x0 + hdim]) + to_f32(bias[d + hdim]);
-    const float gp = to_f32(hg[g0 + 2 * hdim]) + to_f32(xg[x0 + 2 * hdim]) + to_f32(bias[d + 2 * hdim]);
-    const float op = to_f32(hg[g0 + 3 * hdim]) + to_f32(xg[x0 + 3 * hdim]) + to_f32(bias[d + 3 * hdim]);
+    const bool has_prev = b < prev_rows;
+    float hg_i = 0.0f, hg_f = 0.0f, hg_g = 0.0f, hg_o = 0.0f, cp = 0.0f;
+    if (has_prev) {
+      hg_i = to_f32(hg[g0]);
+      hg_f = to_f32(hg[g0 + hdim]);
+      hg_g = to_f32(hg[g0 + 2 * hdim]);
+      hg_o = to_f32(hg[g0 + 3 * hdim]);
+      cp = to_f32(c_prev[t]);
+    }
+    const float ip = hg_i + to_f32(xg[x0]) + to_f32(bias[d]);
+    const float fp = hg_f + to_f32(xg[x0 + hdim]) + to_f32(bias[d + hdim]);
+    const float gp = hg_g + to_f32(xg[x0 + 2 * hdim]) + to_f32(bias[d + 2 * hdim]);
+    const float op = hg_o + to_f32(xg[x0 + 3 * hdim]) + to_f32(bias[d + 3 * hdim]);
     const float i = sigmoidf_(ip);
     const float f = sigmoidf_(fp);
     const float g = tanhf(gp);
     const float o = sigmoidf_(op);
-    const float cp = to_f32(c_prev[t]);
     float cn = f * cp + i * g;
     float hn = o * tanhf(cn);
     if (mask != nullptr) {
       const float m = mask[b];
+      const float hp = has_prev ? to_f32(h_prev[b * hprev_stride + d]) : 0.0f;
       cn = m * cn + (1.0f - m) * cp;
-      hn = m * hn + (1.0f - m) * to_f32(h_prev[b * hprev_stride + d]);
+      hn = m * hn + (1.0f - m) * hp;
     }
     c_out[t] = from_f32<T>(cn);
     h_out[b * hout_stride + d] = from_f32<T>(hn);
@@ -77,8 +91,9 @@ __global__ void lstm_pointwise_bwd_kernel(
     const float* __restrict__ mask,   // [B] or nullptr
     T* __restrict__ grad_gates,       // [B(row-stride gg_stride), 4H]
     T* __restrict__ grad_c_prev,      // [B, H]
-    T* __restrict__ grad_h_pass,      // [B, H]
-    long batch, int hdim, long gout_stride, long gg_stride) {
+    T* __restrict__ grad_h_pass,      // [B, H] or nullptr (no mask: all 0)
+    long batch, int hdim, long gout_stride, long gg_stride, long in_rows,
+    long prev_rows) {
   const long total = batch * hdim;
   for (long t = blockIdx.x * (long)blockDim.x + threadIdx.x; t < total;
        t += (long)gridDim.x * blockDim.x) {
@@ -90,12 +105,13 @@ __global__ void lstm_pointwise_bwd_kernel(
     const float f = to_f32(gates_act[g0 + hdim]);
     const float g = to_f32(gates_act[g0 + 2 * hdim]);
     const float o = to_f32(gates_act[g0 + 3 * hdim]);
-    const float cp = to_f32(c_prev[t]);
+    const float cp = (b < prev_rows) ? to_f32(c_prev[t]) : 0.0f;
     const float m = (mask != nullptr) ? mask[b] : 1.0f;
     const float tcn = tanhf(f * cp + i * g);  // tanh of UNMASKED c_new
-    float gh_in = to_f32(grad_h[t]);
+    const bool has_in = b < in_rows;
+    float gh_in = has_in ? to_f32(grad_h[t]) : 0.0f;
     if (grad_out_t != nullptr) gh_in += to_f32(grad_out_t[b * gout_stride + d]);
-    const float gc_in = to_f32(grad_c[t]);
+    const float gc_in = has_in ? to_f32(grad_c[t]) : 0.0f;
     const float gh = gh_in * m;
     const float gc = gc_in * m;
     const float d_o = gh * tcn;
@@ -104,7 +120,7 @@ __global__ void lstm_pointwise_bwd_kernel(
     const float d_f = d_c * cp;
     const float d_g = d_c * i;
     grad_c_prev[t] = from_f32<T>(d_c * f + gc_in * (1.0f - m));
-    grad_h_pass[t] = from_f32<T>(gh_in * (1.0f - m));
+    if (grad_h_pass != nullptr) grad_h_pass[t] = from_f32<T>(gh_in * (1.0f - m));
     grad_gates[o0] = from_f32<T>(d_i * i * (1.0f - i));
     grad_gates[o0 + hdim] = from_f32<T>(d_f * f * (1.0f - f));
     grad_gates[o0 + 2 * hdim] = from_f32<T>(d_g * (1.0f - g * g));
@@ -130,7 +146,7 @@ __global__ void lstm_pointwise_fwd_vec_kernel(
     const T* __restrict__ h_prev, const float* __restrict__ mask,
     T* __restrict__ h_out, T* __restrict__ c_out, T* __restrict__ gates_act,
     long batch, int hdim, long xg_stride, long hout_stride,
-    long hprev_stride) {
+    long hprev_stride, long prev_rows) {
   using VT = VecT<T, V>;
   const int hv = hdim / V;
   const long total = batch * hv;
@@ -141,10 +157,21 @@ __global__ void lstm_pointwise_fwd_vec_kernel(
     const long g0 = b * 4 * hdim + dv;
     const long x0 = b * xg_stride + dv;
     const long c0 = b * (long)hdim + dv;
-    const VT hg_i = *reinterpret_cast<const VT*>(hg + g0);
-    const VT hg_f = *reinterpret_cast<const VT*>(hg + g0 + hdim);
-    const VT hg_g = *reinterpret_cast<const VT*>(hg + g0 + 2 * hdim);
-    const VT hg_o = *reinterpret_cast<const VT*>(hg + g0 + 3 * hdim);
+    // rows past the previous state start from zero and read none of it
+    const bool has_prev = b < prev_rows;
+    VT hg_i, hg_f, hg_g, hg_o, cp_v;
+    if (has_prev) {
+      hg_i = *reinterpret_cast<const VT*>(hg + g0);
+      hg_f = *reinterpret_cast<const VT*>(hg + g0 + hdim);
+      hg_g = *reinterpret_cast<const VT*>(hg + g0 + 2 * hdim);
+      hg_o = *reinterpret_cast<const VT*>(hg + g0 + 3 * hdim);
+      cp_v = *reinterpret_cast<const VT*>(c_prev + c0);
+    } else {
+#pragma unroll
+      for (int j = 0; j < V; ++j)
+        hg_i.v[j] = hg_f.v[j] = hg_g.v[j] = hg_o.v[j] = cp_v.v[j] =
+            from_f32<T>(0.0f);
+    }
     const VT xg_i = *reinterpret_cast<const VT*>(xg + x0);
     const VT xg_f = *reinterpret_cast<const VT*>(xg + x0 + hdim);
     const VT xg_g = *reinterpret_cast<const VT*>(xg + x0 + 2 * hdim);
@@ -153,11 +180,16 @@ __global__ void lstm_pointwise_fwd_vec_kernel(
     const VT b_f = *reinterpret_cast<const VT*>(bias + dv + hdim);
     const VT b_g = *reinterpret_cast<const VT*>(bias + dv + 2 * hdim);
     const VT b_o = *reinterpret_cast<const VT*>(bias + dv + 3 * hdim);
-    const VT cp_v = *reinterpret_cast<const VT*>(c_prev + c0);
     VT hp_v;
     const float m = (mask != nullptr) ? mask[b] : 1.0f;
-    if (mask != nullptr)
-      hp_v = *reinterpret_cast<const VT*>(h_prev + b * hprev_stride + dv);
+    if (mask != nullptr) {
+      if (has_prev) {
+        hp_v = *reinterpret_cast<const VT*>(h_prev + b * hprev_stride + dv);
+      } else {
+#pragma unroll
+        for (int j = 0; j < V; ++j) hp_v.v[j] = from_f32<T>(0.0f);
+      }
+    }
     VT ho_v, co_v, ga_i, ga_f, ga_g, ga_o;
 #pragma unroll
     for (int j = 0; j < V; ++j) {
@@ -210,7 +242,8 @@ lstm_pointwise_bwd_vec_kernel(
     const T* __restrict__ c_prev, const float* __restrict__ mask,
     T* __restrict__ grad_gates, T* __restrict__ grad_c_prev,
     T* __restrict__ grad_h_pass, float* __restrict__ bias_accum,
-    long batch, int hdim, long gout_stride, long gg_stride) {
+    long batch, int hdim, long gout_stride, long gg_stride, long in_rows,
+    long prev_rows) {
   using VT = VecT<T, V>;
   float s_i[V], s_f[V], s_g[V], s_o[V];
   if constexpr (ACC) {
@@ -230,9 +263,22 @@ lstm_pointwise_bwd_vec_kernel(
     const VT ga_f = *reinterpret_cast<const VT*>(gates_act + g0 + hdim);
     const VT ga_g = *reinterpret_cast<const VT*>(gates_act + g0 + 2 * hdim);
     const VT ga_o = *reinterpret_cast<const VT*>(gates_act + g0 + 3 * hdim);
-    const VT cp_v = *reinterpret_cast<const VT*>(c_prev + c0);
-    const VT gh_v = *reinterpret_cast<const VT*>(grad_h + c0);
-    const VT gc_v = *reinterpret_cast<const VT*>(grad_c + c0);
+    // rows >= prev_rows had a zero previous cell state; rows >= in_rows
+    // have no incoming recurrent gradient — neither is read there
+    VT cp_v, gh_v, gc_v;
+    if (b < prev_rows) {
+      cp_v = *reinterpret_cast<const VT*>(c_prev + c0);
+    } else {
+#pragma unroll
+      for (int j = 0; j < V; ++j) cp_v.v[j] = from_f32<T>(0.0f);
+    }
+    if (b < in_rows) {
+      gh_v = *reinterpret_cast<const VT*>(grad_h + c0);
+      gc_v = *reinterpret_cast<const VT*>(grad_c + c0);
+    } else {
+#pragma unroll
+      for (int j = 0; j < V; ++j) gh_v.v[j] = gc_v.v[j] = from_f32<T>(0.0f);
+    }
     VT go_v;
     if (grad_out_t != nullptr)
       go_v = *reinterpret_cast<const VT*>(grad_out_t + b * gout_stride + dv);
@@ -281,7 +327,8 @@ lstm_pointwise_bwd_vec_kernel(
       }
     }
     *reinterpret_cast<VT*>(grad_c_prev + c0) = gcp_v;
-    *reinterpret_cast<VT*>(grad_h_pass + c0) = ghp_v;
+    if (grad_h_pass != nullptr)  // without a mask it is identically zero
+      *reinterpret_cast<VT*>(grad_h_pass + c0) = ghp_v;
     *reinterpret_cast<VT*>(grad_gates + o0) = gg_i;
     *reinterpret_cast<VT*>(grad_gates + o0 + hdim) = gg_f;
     *reinterpret_cast<VT*>(grad_gates + o0 + 2 * hdim) = gg_g;
@@ -326,47 +373,9 @@ lstm_pointwise_bwd_vec_kernel(
   }
 }
 
-template __global__ void lstm_pointwise_fwd_vec_kernel<__hip_bfloat16, 8>(
-    const __hip_bfloat16*, const __hip_bfloat16*, const __hip_bfloat16*,
-    const __hip_bfloat16*, const __hip_bfloat16*, const float*,
-    __hip_bfloat16*, __hip_bfloat16*, __hip_bfloat16*, long, int, long, long,
-    long);
-template __global__ void lstm_pointwise_fwd_vec_kernel<float, 4>(
-    const float*, const float*, const float*, const float*, const float*,
-    const float*, float*, float*, float*, long, int, long, long, long);
-template __global__ void lstm_pointwise_bwd_vec_kernel<__hip_bfloat16, 8, false>(
-    const __hip_bfloat16*, const __hip_bfloat16*, const __hip_bfloat16*,
-    const __hip_bfloat16*, const __hip_bfloat16*, const float*,
-    __hip_bfloat16*, __hip_bfloat16*, __hip_bfloat16*, float*, long, int,
-    long, long);
-template __global__ void lstm_pointwise_bwd_vec_kernel<float, 4, false>(
-    const float*, const float*, const float*, const float*, const float*,
-    const float*, float*, float*, float*, float*, long, int, long, long);
-template __global__ void lstm_pointwise_bwd_vec_kernel<__hip_bfloat16, 8, true>(
-    const __hip_bfloat16*, const __hip_bfloat16*, const __hip_bfloat16*,
-    const __hip_bfloat16*, const __hip_bfloat16*, const float*,
-    __hip_bfloat16*, __hip_bfloat16*, __hip_bfloat16*, float*, long, int,
-    long, long);
-template __global__ void lstm_pointwise_bwd_vec_kernel<float, 4, true>(
-    const float*, const float*, const float*, const float*, const float*,
-    const float*, float*, float*, float*, float*, long, int, long, long);
-
-template __global__ void lstm_pointwise_fwd_kernel<float>(
-    const float*, const float*, const float*, const float*, const float*, const float*,
-    float*, float*, float*, long, int, long, long, long);
-template __global__ void lstm_pointwise_fwd_kernel<__hip_bfloat16>(
-    const __hip_bfloat16*, const __hip_bfloat16*, const __hip_bfloat16*, const __hip_bfloat16*,
-    const __hip_bfloat16*, const float*, __hip_bfloat16*, __hip_bfloat16*, __hip_bfloat16*,
-    long, int, long, long, long);
-template __global__ void lstm_pointwise_bwd_kernel<float>(
-    const float*, const float*, const float*, const float*, const float*, const float*,
-    float*, float*, float*, long, int, long, long);
-template __global__ void lstm_pointwise_bwd_kernel<__hip_bfloat16>(
-    const __hip_bfloat16*, const __hip_bfloat16*, const __hip_bfloat16*, const __hip_bfloat16*,
-    const __hip_bfloat16*, const float*, __hip_bfloat16*, __hip_bfloat16*, __hip_bfloat16*, long, int, long, long);
-
 // ---------------------------------------------------------------------------
-// host launchers
+// host launchers (they instantiate every kernel variant above).  A launch
+// over zero rows is a no-op: a grid of 0 blocks is a launch error.
 // ---------------------------------------------------------------------------
 
 static inline int grid_elems(long total, int block) {
@@ -381,7 +390,9 @@ void launch_lstm_pointwise_fwd(const void* hg, const void* xg, const void* bias,
                                const float* mask, void* h_out, void* c_out,
                                void* gates_act, long batch, int hdim,
                                long xg_stride, long hout_stride,
-                               long hprev_stride, bool bf16, hipStream_t s) {
+                               long hprev_stride, long prev_rows, bool bf16,
+                               hipStream_t s) {
+  if (batch <= 0) return;
   const int block = 256;
   // vectorised path (16-B global accesses) whenever the layout allows
   const int v = bf16 ? 8 : 4;
@@ -395,7 +406,7 @@ void launch_lstm_pointwise_fwd(const void* hg, const void* xg, const void* bias,
           (const __hip_bfloat16*)bias, (const __hip_bfloat16*)c_prev,
           (const __hip_bfloat16*)h_prev, mask, (__hip_bfloat16*)h_out,
           (__hip_bfloat16*)c_out, (__hip_bfloat16*)gates_act, batch, hdim,
-          xg_stride, hout_stride, hprev_stride);
+          xg_stride, hout_stride, hprev_stride, prev_rows);
       return;
     }
     const int grid = grid_elems(batch * hdim, block);
@@ -404,7 +415,7 @@ void launch_lstm_pointwise_fwd(const void* hg, const void* xg, const void* bias,
         (const __hip_bfloat16*)bias, (const __hip_bfloat16*)c_prev,
         (const __hip_bfloat16*)h_prev, mask, (__hip_bfloat16*)h_out,
         (__hip_bfloat16*)c_out, (__hip_bfloat16*)gates_act, batch, hdim,
-        xg_stride, hout_stride, hprev_stride);
+        xg_stride, hout_stride, hprev_stride, prev_rows);
   } else {
     if (vec) {
       const int grid = grid_elems(batch * (hdim / v), block);
@@ -412,7 +423,7 @@ void launch_lstm_pointwise_fwd(const void* hg, const void* xg, const void* bias,
           (const float*)hg, (const float*)xg, (const float*)bias,
           (const float*)c_prev, (const float*)h_prev, mask, (float*)h_out,
           (float*)c_out, (float*)gates_act, batch, hdim, xg_stride,
-          hout_stride, hprev_stride);
+          hout_stride, hprev_stride, prev_rows);
       return;
     }
     const int grid = grid_elems(batch * hdim, block);
@@ -420,7 +431,7 @@ void launch_lstm_pointwise_fwd(const void* hg, const void* xg, const void* bias,
         (const float*)hg, (const float*)xg, (const float*)bias,
         (const float*)c_prev, (const float*)h_prev, mask, (float*)h_out,
         (float*)c_out, (float*)gates_act, batch, hdim, xg_stride, hout_stride,
-        hprev_stride);
+        hprev_stride, prev_rows);
   }
 }
 
@@ -435,7 +446,8 @@ static void launch_bwd_vec(const void* grad_h, const void* grad_out_t,
                            void* grad_gates, void* grad_c_prev,
                            void* grad_h_pass, float* accum, long accum_rows,
                            long batch, int hdim, long gout_stride,
-                           long gg_stride, hipStream_t s) {
+                           long gg_stride, long in_rows, long prev_rows,
+                           hipStream_t s) {
   const int block = 256;  // the accumulating kernel relies on 256
   const int hv = hdim / V;
   if (accum != nullptr) {
@@ -449,7 +461,7 @@ static void launch_bwd_vec(const void* grad_h, const void* grad_out_t,
         (const T*)grad_h, (const T*)grad_out_t, (const T*)grad_c,
         (const T*)gates_act, (const T*)c_prev, mask, (T*)grad_gates,
         (T*)grad_c_prev, (T*)grad_h_pass, accum, batch, hdim, gout_stride,
-        gg_stride);
+        gg_stride, in_rows, prev_rows);
     return;
   }
   const int grid = grid_elems(batch * hv, block);
@@ -457,7 +469,7 @@ static void launch_bwd_vec(const void* grad_h, const void* grad_out_t,
       (const T*)grad_h, (const T*)grad_out_t, (const T*)grad_c,
       (const T*)gates_act, (const T*)c_prev, mask, (T*)grad_gates,
       (T*)grad_c_prev, (T*)grad_h_pass, nullptr, batch, hdim, gout_stride,
-      gg_stride);
+      gg_stride, in_rows, prev_rows);
 }
 
 // Returns true when the bias-gradient partial was folded into bias_accum
@@ -470,8 +482,9 @@ bool launch_lstm_pointwise_bwd(const void* grad_h, const void* grad_out_t,
                                void* grad_gates, void* grad_c_prev,
                                void* grad_h_pass, float* bias_accum,
                                long accum_rows, long batch, int hdim,
-                               long gout_stride, long gg_stride, bool bf16,
-                               hipStream_t s) {
+                               long gout_stride, long gg_stride, long in_rows,
+                               long prev_rows, bool bf16, hipStream_t s) {
+  if (batch <= 0) return false;
   const int block = 256;
   const int v = bf16 ? 8 : 4;
   const bool vec = hdim % v == 0 && gout_stride % v == 0 && gg_stride % v == 0;
@@ -483,7 +496,7 @@ bool launch_lstm_pointwise_bwd(const void* grad_h, const void* grad_out_t,
       launch_bwd_vec<__hip_bfloat16, 8>(
           grad_h, grad_out_t, grad_c, gates_act, c_prev, mask, grad_gates,
           grad_c_prev, grad_h_pass, accum, accum_rows, batch, hdim,
-          gout_stride, gg_stride, s);
+          gout_stride, gg_stride, in_rows, prev_rows, s);
       return acc;
     }
     const int grid = grid_elems(batch * hdim, block);
@@ -492,13 +505,13 @@ bool launch_lstm_pointwise_bwd(const void* grad_h, const void* grad_out_t,
         (const __hip_bfloat16*)grad_c, (const __hip_bfloat16*)gates_act,
         (const __hip_bfloat16*)c_prev, mask, (__hip_bfloat16*)grad_gates,
         (__hip_bfloat16*)grad_c_prev, (__hip_bfloat16*)grad_h_pass, batch, hdim,
-        gout_stride, gg_stride);
+        gout_stride, gg_stride, in_rows, prev_rows);
   } else {
     if (vec) {
       launch_bwd_vec<float, 4>(
           grad_h, grad_out_t, grad_c, gates_act, c_prev, mask, grad_gates,
           grad_c_prev, grad_h_pass, accum, accum_rows, batch, hdim,
-          gout_stride, gg_stride, s);
+          gout_stride, gg_stride, in_rows, prev_rows, s);
       return acc;
     }
     const int grid = grid_elems(batch * hdim, block);
@@ -506,7 +519,7 @@ bool launch_lstm_pointwise_bwd(const void* grad_h, const void* grad_out_t,
         (const float*)grad_h, (const float*)grad_out_t, (const float*)grad_c,
         (const float*)gates_act, (const float*)c_prev, mask, (float*)grad_gates,
         (float*)grad_c_prev, (float*)grad_h_pass, batch, hdim, gout_stride,
-        gg_stride);
+        gg_stride, in_rows, prev_rows);
   }
   return false;
 }

@@ -164,6 +164,7 @@ __global__ void rec_gemm_fwd_kernel(
 
 void launch_rec_gemm_fwd(const void* a, const void* w, void* c, long m_rows,
                          long a_stride, long c_stride, hipStream_t s) {
+  if (m_rows <= 0) return;  // a grid of 0 blocks is a launch error
   const int grid = (int)((m_rows + RG_BM - 1) / RG_BM);
   const size_t lds = RG_BM * 512 + 8 * 1024;  // 64 KB A + 8 KB staging
   rec_gemm_fwd_kernel<<<grid, 512, lds, s>>>(

@@ -35,13 +35,26 @@ the backward path (no narrow+contiguous copies of the per-direction grads).
 This removes the per-step elementwise adds / stacks / reduces that dominated
 the naive schedule (profiles/: 84% of busy time before the restructure).
 Everything is time-major [T, B, ...]; the model transposes once per sequence.
+
+`lstm_bilayer2_packed` is the training layer op.  It runs the split path
+over a length-sorted packed layout (`SeqPlan`): every LSTM tensor holds only
+the N = sum(lengths) live (timestep, sequence) rows, and both directions loop
+over max(lengths) steps instead of T.  The dense masked ops above compute,
+store and read back a row for every padded position (62.6 % of the rows of
+the benchmark batch) and stay for inference and for A/B runs
+(NERRF_LSTM_PACKED=0, read by the model).  The packed path has no mask: the
+pointwise kernels take row counts instead (`prev_rows`, `in_rows`), so a
+step may cover more rows than its predecessor produced without a zero-fill.
 """
 from __future__ import annotations
 
 import contextlib
+import dataclasses
 import os
-from typing import Optional
+from dataclasses import dataclass
+from typing import List, Optional, Tuple
 
+import numpy as np
 import torch
 
 from . import reference as _ref
@@ -490,3 +503,332 @@ def lstm_bilayer2(
     return _LSTMBiLayer2Fn.apply(
         xg2, h0, c0, w_f, b_f, w_b, b_b, _norm_mask(mask), infer
     )
+
+
+# ---------------------------------------------------------------------------
+# packed (length-sorted) bidirectional layer
+# ---------------------------------------------------------------------------
+
+# Below this many rows the recurrent step GEMM goes to hipBLASLt even where
+# rec_gemm.hip's shape contract holds.  rec_gemm loses to hipBLASLt below
+# ~32k rows (0.73x at M=16k, 0.93x at 24k, 1.04x at 32k, 1.18x at 64k:
+# tools/rec_gemm_ab.py; profiles/PROFILES.md, "Packed BiLSTM"), but the two
+# round differently and the dense path runs rec_gemm on every step: with the
+# threshold at 1 the packed forward is bitwise the dense forward
+# (tests/test_lstm_packed_gpu.py).  That is worth the ~2 ms/step (113.4 ->
+# 115.7) which a threshold at the crossover saves on the benchmark.
+_REC_GEMM_MIN_ROWS = 1
+
+
+@dataclass
+class SeqPlan:
+    """Length-sorted packing of a padded [B, T] batch of sequences.
+
+    Sequences are sorted by (clamped) length, descending and stable; sorted
+    row r is sequence perm[r].  At timestep t the live sequences are the
+    sorted rows [0, batch_sizes[t]) and batch_sizes is non-increasing, so a
+    packed time-major tensor has N = sum(lengths) rows: slab t sits at rows
+    [offsets[t], offsets[t] + batch_sizes[t]).  Timesteps at or past
+    max(lengths) do not exist.  perm, inv_perm, batch_sizes and offsets live
+    on the host; the index tensors on the device the op runs on, so a step
+    that is handed a plan does no device-to-host copy.
+    """
+
+    n_seq: int                 # B
+    t_max: int                 # padded length T the lengths were clamped to
+    perm: np.ndarray           # [B] sorted row -> sequence
+    inv_perm: np.ndarray       # [B] sequence -> sorted row
+    batch_sizes: List[int]     # [T_live] n_t
+    offsets: List[int]         # [T_live + 1] off_t, offsets[-1] == N
+    has_empty: bool            # some sequence has length 0
+    pack_idx: torch.Tensor     # [N] rows of feats.reshape(B*T, E)
+    hin_idx: torch.Tensor      # [2N] rows of the [(N+1)*2, H] view of the
+    #                            layer output (+1: a trailing zero row) that
+    #                            form the steps' h inputs, both directions
+    fin_idx: torch.Tensor      # [2B] rows of the [2N, H] view holding each
+    #                            sequence's final fwd / bwd state
+    live: torch.Tensor         # [B, 1] f32, 0 where length == 0
+
+    def to(self, device) -> "SeqPlan":
+        """The same plan with its index tensors on `device` (host fields
+        shared) — building a plan costs ~0.15 s of numpy at B = 64k, so a
+        batch builds it once on the CPU and stages it per use."""
+        device = torch.device(device)
+        if self.pack_idx.device == device:
+            return self
+        moved = {
+            k: getattr(self, k).to(device, non_blocking=True)
+            for k in ("pack_idx", "hin_idx", "fin_idx", "live")
+        }
+        return dataclasses.replace(self, **moved)
+
+    @property
+    def n_rows(self) -> int:
+        return self.offsets[-1]
+
+    @property
+    def t_live(self) -> int:
+        return len(self.batch_sizes)
+
+    def steps(self, reverse: bool) -> List[Tuple[int, int, int, int]]:
+        """(off, n, prev_off, k) per step in execution order: the step
+        covers rows [off, off + n); its previous state is the first k rows
+        of the slab at prev_off (k == 0: zero initial state)."""
+        n, off = self.batch_sizes, self.offsets
+        tl = len(n)
+        if reverse:
+            return [
+                (off[t], n[t], off[t + 1], n[t + 1] if t + 1 < tl else 0)
+                for t in range(tl - 1, -1, -1)
+            ]
+        return [
+            (off[t], n[t], off[t - 1] if t else 0, n[t] if t else 0)
+            for t in range(tl)
+        ]
+
+
+def build_seq_plan(lengths, t_max: int, device="cpu") -> SeqPlan:
+    """Plan from `lengths` ([B]; numpy array or tensor — a device tensor
+    costs one device-to-host copy here).  Lengths are clamped to
+    [0, t_max]."""
+    if isinstance(lengths, torch.Tensor):
+        lengths = lengths.detach().cpu().numpy()
+    ln = np.clip(np.asarray(lengths).astype(np.int64).reshape(-1), 0, int(t_max))
+    b = int(ln.shape[0])
+    perm = np.argsort(-ln, kind="stable")
+    inv_perm = np.empty(b, dtype=np.int64)
+    inv_perm[perm] = np.arange(b, dtype=np.int64)
+    t_live = int(ln.max()) if b else 0
+    # n_t = number of sequences longer than t
+    n_t = b - np.cumsum(np.bincount(ln, minlength=t_live + 1))[:t_live]
+    off = np.zeros(t_live + 1, dtype=np.int64)
+    np.cumsum(n_t, out=off[1:])
+    n_rows = int(off[-1])
+
+    t_of = np.repeat(np.arange(t_live, dtype=np.int64), n_t)  # [N]
+    r_of = np.arange(n_rows, dtype=np.int64) - off[t_of]
+    pack_idx = perm[r_of] * int(t_max) + t_of
+    # h input of packed row (t, r).  Forward direction: row r of slab t-1
+    # (slab 0 starts from zero).  Reverse: row r of slab t+1 where that slab
+    # has such a row, else zero.  Zero = row N of the padded layer output.
+    src_f = np.where(t_of > 0, off[np.maximum(t_of - 1, 0)] + r_of, n_rows)
+    n_next = np.append(n_t, 0)[t_of + 1] if t_live else n_t
+    src_b = np.where(r_of < n_next, off[np.minimum(t_of + 1, t_live)] + r_of, n_rows)
+    hin_idx = np.stack([2 * src_f, 2 * src_b + 1], axis=1).reshape(-1)
+    # final states per sequence, in the original order
+    r_seq = inv_perm
+    live = ln > 0
+    fin_f = np.where(live, off[np.maximum(ln - 1, 0)] + r_seq, 0)
+    fin_b = np.where(live, r_seq, 0)
+    fin_idx = np.stack([2 * fin_f, 2 * fin_b + 1], axis=1).reshape(-1)
+
+    def dev(a, dt=torch.int64):
+        return torch.from_numpy(np.ascontiguousarray(a)).to(dt).to(device, non_blocking=True)
+
+    return SeqPlan(
+        n_seq=b, t_max=int(t_max), perm=perm, inv_perm=inv_perm,
+        batch_sizes=[int(x) for x in n_t], offsets=[int(x) for x in off],
+        has_empty=bool((~live).any()),
+        pack_idx=dev(pack_idx), hin_idx=dev(hin_idx), fin_idx=dev(fin_idx),
+        live=dev(live.reshape(b, 1), torch.float32),
+    )
+
+
+def _packed_dir_forward(ext, xg, w_hh, bias, plan, reverse, infer, h_out,
+                        c_all, gates_all, hg):
+    """One direction over the packed layout.  xg [N, 4H], h_out [N, H] (rows
+    uniformly strided: slabs of the dual-direction buffers); c_all [N, H],
+    gates_all [N, 4H] contiguous; hg: [n_0, 4H] scratch, sliced per step —
+    rows past a step's k hold stale data of a longer step and are never
+    read (prev_rows)."""
+    dt, hdim = xg.dtype, w_hh.shape[1]
+    if ext is None:
+        for off, n, poff, k in plan.steps(reverse):
+            pre = xg[off:off + n] + bias
+            c_in = pre.new_zeros(n, hdim)
+            if k:
+                pre[:k] += h_out[poff:poff + k] @ w_hh.t()
+                c_in[:k] = c_all[poff:poff + k]
+            h_new, c_new, g_act = _ref.lstm_pointwise_fwd_ref(pre, c_in, None, None)
+            h_out[off:off + n] = h_new
+            c_all[off:off + n] = c_new
+            if not infer:
+                gates_all[off:off + n] = g_act
+        return
+    mfma = _mfma_eligible(dt, hdim, w_hh)
+    use_rg = (
+        mfma and os.environ.get("NERRF_REC_GEMM", "1") == "1"
+        and h_out.stride(0) % 8 == 0
+    )
+    w_hh_t = w_hh.t().contiguous()
+    g_none = torch.empty(0, device=xg.device, dtype=dt)
+    empty_mask = torch.empty(0, device=xg.device)
+    for off, n, poff, k in plan.steps(reverse):
+        h_prev = h_out[poff:poff + k]
+        if k:  # no zero-row GEMMs
+            if use_rg and k >= _REC_GEMM_MIN_ROWS:
+                ext.rec_gemm_fwd(h_prev, w_hh, hg[:k])
+            else:
+                torch.mm(h_prev, w_hh_t, out=hg[:k])
+        ext.lstm_pointwise_fwd(
+            hg[:k], xg[off:off + n], bias, c_all[poff:poff + k], h_prev,
+            empty_mask, h_out[off:off + n], c_all[off:off + n],
+            g_none if infer else gates_all[off:off + n], k,
+        )
+
+
+def _packed_dir_backward(ext, grad_out, gates_all, c_all, w_hh, plan, reverse,
+                         gg_out):
+    """Backward of `_packed_dir_forward`: fills gg_out [N, 4H] (a slab of
+    the dual gate-grad buffer) and returns the bias gradient source: the f32
+    slab the kernel accumulated into, or None (reduce gg_out instead)."""
+    dt, dev = c_all.dtype, c_all.device
+    hdim = w_hh.shape[1]
+    steps = plan.steps(reverse)
+    n0 = plan.batch_sizes[0]
+    # the step after s in execution order consumed the first k rows of s's
+    # output, so that is how many rows of recurrent gradient s receives
+    in_rows = [st[3] for st in steps[1:]] + [0]
+    if ext is None:
+        grad_h = grad_c = None
+        for (off, n, poff, k), rin in zip(reversed(steps), reversed(in_rows)):
+            gh_in = grad_out[off:off + n].clone()
+            gc_in = gh_in.new_zeros(n, hdim)
+            c_in = gh_in.new_zeros(n, hdim)
+            if rin:
+                gh_in[:rin] += grad_h[:rin]
+                gc_in[:rin] = grad_c[:rin]
+            if k:
+                c_in[:k] = c_all[poff:poff + k]
+            gg, gc_prev, _ = _ref.lstm_pointwise_bwd_ref(
+                gh_in, gc_in, gates_all[off:off + n], c_in, None
+            )
+            gg_out[off:off + n] = gg
+            grad_h, grad_c = gg[:k] @ w_hh, gc_prev[:k]
+        return None
+    slab_on = os.environ.get("NERRF_FUSED_BIAS", "1") == "1"
+    empty = torch.empty(0, device=dev)
+    slab = (
+        torch.zeros(_bias_slab_rows(n0, hdim, dt), 4 * hdim, device=dev,
+                    dtype=torch.float32)
+        if slab_on else empty
+    )
+    slab_used = slab_on
+    # without a mask the pass-through gradient is identically zero: the
+    # kernel skips its store and the recurrent dgrad is a plain mm into the
+    # one grad_h buffer (the kernel that read it ran before, same stream)
+    grad_h = torch.empty(n0, hdim, device=dev, dtype=dt)
+    grad_c = torch.empty(n0, hdim, device=dev, dtype=dt)
+    spare_c = torch.empty(n0, hdim, device=dev, dtype=dt)
+    no_pass = torch.empty(0, device=dev, dtype=dt)
+    for (off, n, poff, k), rin in zip(reversed(steps), reversed(in_rows)):
+        gg_t = gg_out[off:off + n]
+        used = ext.lstm_pointwise_bwd(
+            grad_h[:rin], grad_out[off:off + n], grad_c[:rin],
+            gates_all[off:off + n], c_all[poff:poff + k], empty, gg_t,
+            spare_c[:n], no_pass, slab, rin, k,
+        )
+        slab_used = slab_used and bool(used)
+        if k:  # dgrad only on the rows the next step consumes
+            torch.mm(gg_t[:k], w_hh, out=grad_h[:k])
+        grad_c, spare_c = spare_c, grad_c
+    return slab if slab_used else None
+
+
+class _LSTMBiLayer2PackedFn(torch.autograd.Function):
+    """`_LSTMBiLayer2Fn` over the packed layout: xg2p [N, 2*4H] -> h2p
+    [N, 2H], zero initial state, no mask — padding rows do not exist."""
+
+    @staticmethod
+    def forward(ctx, xg2p, w_f, b_f, w_b, b_b, plan: SeqPlan, infer: bool = False):
+        n_rows, gdim2 = xg2p.shape
+        gdim = gdim2 // 2
+        hdim = gdim // 4
+        dev, dt = xg2p.device, xg2p.dtype
+        ext = get_native(xg2p)
+        # one extra, zero row: the h input of a step's rows that have no
+        # previous state (see SeqPlan.hin_idx)
+        h2p_buf = torch.empty(n_rows + 1, 2 * hdim, device=dev, dtype=dt)
+        h2p_buf[n_rows].zero_()
+        h2p = h2p_buf[:n_rows]
+        c_f = torch.empty(n_rows, hdim, device=dev, dtype=dt)
+        c_b = torch.empty(n_rows, hdim, device=dev, dtype=dt)
+        g_rows = 0 if infer else n_rows
+        g_f = torch.empty(g_rows, gdim, device=dev, dtype=dt)
+        g_b = torch.empty(g_rows, gdim, device=dev, dtype=dt)
+        hg = (
+            torch.empty(plan.batch_sizes[0], gdim, device=dev, dtype=dt)
+            if ext is not None and n_rows else None
+        )
+        _packed_dir_forward(ext, xg2p[:, :gdim], w_f, b_f, plan, False, infer,
+                            h2p[:, :hdim], c_f, g_f, hg)
+        _packed_dir_forward(ext, xg2p[:, gdim:], w_b, b_b, plan, True, infer,
+                            h2p[:, hdim:], c_b, g_b, hg)
+        ctx.save_for_backward(g_f, g_b, h2p_buf, c_f, c_b, w_f, w_b)
+        ctx.plan = plan
+        return h2p
+
+    @staticmethod
+    def backward(ctx, grad2):
+        g_f, g_b, h2p_buf, c_f, c_b, w_f, w_b = ctx.saved_tensors
+        plan = ctx.plan
+        n_rows = h2p_buf.shape[0] - 1
+        hdim = h2p_buf.shape[1] // 2
+        gdim = 4 * hdim
+        dev, dt = h2p_buf.device, h2p_buf.dtype
+        ext = get_native(h2p_buf)
+        grad2 = grad2.contiguous()
+        # ONE [N, 2*4H] gate-grad buffer: the projection's dgrad / wgrad
+        # stay single GEMMs
+        gg2 = torch.empty(n_rows, 2 * gdim, device=dev, dtype=dt)
+        if n_rows == 0:
+            zw = torch.zeros_like(w_f)
+            zb = torch.zeros(gdim, device=dev, dtype=dt)
+            return gg2, zw, zb, zw.clone(), zb.clone(), None, None
+        slab_f = _packed_dir_backward(ext, grad2[:, :hdim], g_f, c_f, w_f,
+                                      plan, False, gg2[:, :gdim])
+        slab_b = _packed_dir_backward(ext, grad2[:, hdim:], g_b, c_b, w_b,
+                                      plan, True, gg2[:, gdim:])
+        # recurrent weight grads: one GEMM per direction over all live rows
+        n0 = plan.batch_sizes[0]
+        if plan.batch_sizes[-1] == n0:
+            # all sequences equally long: every slab has n0 rows, so the
+            # steps' h inputs are the history shifted by one slab — views
+            # (the edge slab's h input is zero and drops out)
+            if n_rows > n0:
+                gw_f = torch.mm(gg2[n0:, :gdim].t(), h2p_buf[:n_rows - n0, :hdim])
+                gw_b = torch.mm(gg2[:n_rows - n0, gdim:].t(), h2p_buf[n0:n_rows, hdim:])
+            else:
+                gw_f, gw_b = torch.zeros_like(w_f), torch.zeros_like(w_b)
+        else:
+            # slabs differ in size, so the shifted history is not a view:
+            # both directions' h inputs as ONE [N, 2H] gather
+            h_in = (
+                h2p_buf.view(2 * (n_rows + 1), hdim)
+                .index_select(0, plan.hin_idx).view(n_rows, 2 * hdim)
+            )
+            gw_f = torch.mm(gg2[:, :gdim].t(), h_in[:, :hdim])
+            gw_b = torch.mm(gg2[:, gdim:].t(), h_in[:, hdim:])
+        gb_f = (slab_f.sum(dim=0).to(dt) if slab_f is not None
+                else gg2[:, :gdim].sum(dim=0))
+        gb_b = (slab_b.sum(dim=0).to(dt) if slab_b is not None
+                else gg2[:, gdim:].sum(dim=0))
+        return gg2, gw_f, gb_f, gw_b, gb_b, None, None
+
+
+def lstm_bilayer2_packed(
+    xg2p: torch.Tensor,  # [N, 2*4H] packed: fwd projection 0:4H, bwd 4H:8H
+    plan: SeqPlan,
+    w_f: torch.Tensor,
+    b_f: torch.Tensor,
+    w_b: torch.Tensor,
+    b_b: torch.Tensor,
+) -> torch.Tensor:
+    """Both directions of one layer over length-sorted packed rows ->
+    [N, 2H] (fwd cols 0:H, bwd H:2H).  Every LSTM tensor holds only the
+    N = sum(lengths) live (timestep, sequence) rows, both directions loop
+    over max(lengths) steps, and the state starts from zero."""
+    assert xg2p.dim() == 2 and xg2p.stride(1) == 1, "xg2p rows must be contiguous"
+    assert xg2p.shape[0] == plan.n_rows, "xg2p does not match the plan"
+    infer = _infer_mode(xg2p, w_f, b_f, w_b, b_b)
+    return _LSTMBiLayer2PackedFn.apply(xg2p, w_f, b_f, w_b, b_b, plan, infer)

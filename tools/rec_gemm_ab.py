@@ -1,7 +1,9 @@
 """A/B: rec_gemm_fwd (rec_gemm.hip) vs tuned hipBLASLt on the recurrent
 step shape hg[B,1024] = h[B,256] @ W_hh[1024,256]^T.
 
-Run on a GPU box:  python tools/rec_gemm_ab.py
+Run on a GPU box:  python tools/rec_gemm_ab.py [M ...]
+(row counts of the forward A/B; default 16384 65536 — the packed sequence op
+picks between the two per step by row count, see `_REC_GEMM_MIN_ROWS`).
 """
 import os
 import sys
@@ -20,7 +22,7 @@ ext = load_extension(required=True)
 dev = "cuda:0"
 torch.manual_seed(0)
 
-for m in (16384, 65536):
+for m in tuple(int(x) for x in sys.argv[1:]) or (16384, 65536):
     a = (torch.randn(m, 256, device=dev) * 0.1).to(torch.bfloat16)
     w = (torch.randn(1024, 256, device=dev) * 0.1).to(torch.bfloat16)
     wt = w.t().contiguous()
@@ -57,8 +59,8 @@ for m in (16384, 65536):
     t_blas = bench(lambda: torch.mm(a, wt, out=c_ref))
     t_k = bench(lambda: ext.rec_gemm_fwd(a, w, c_k))
     gb = (m * 256 * 2 + m * 1024 * 2 + 1024 * 256 * 2) / 1e9
-    print(f"M={m}: blas {t_blas:.1f} us ({gb / (t_blas * 1e-6):.2f} TB/s eff)"
-          f" | rec_gemm {t_k:.1f} us ({gb / (t_k * 1e-6):.2f} TB/s eff)"
+    print(f"M={m}: blas {t_blas:.1f} us ({gb / (t_blas * 1e-6) / 1e3:.2f} TB/s eff)"
+          f" | rec_gemm {t_k:.1f} us ({gb / (t_k * 1e-6) / 1e3:.2f} TB/s eff)"
           f" | speedup {t_blas / t_k:.2f}x")
 
 # ---- dgrad: grad_h = gg @ W_hh (+ grad_h_pass) -----------------------------
