@@ -188,6 +188,7 @@ def cmd_serve(args) -> int:
         engine = StreamingEngine(model=model, device=args.device, dtype=dtype)
         from .serve.registry import DEFAULT_STATE_DIR, DetectionRegistry
 
+        # each status line carries the top edge hit of an alarmed window
         for status in engine.run_monitor(
             interval_s=args.interval,
             max_iterations=args.iterations,
@@ -230,6 +231,8 @@ def cmd_serve(args) -> int:
                 "attack_id": attack_id,
                 "indicators": det.indicators,
                 "suspicious_files": det.encrypted_paths[:10],
+                "top_edge": (det.top_edges[0].as_dict()
+                             if det.alarm and det.top_edges else None),
             },
             indent=2,
         )

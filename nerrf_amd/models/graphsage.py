@@ -117,5 +117,23 @@ class GraphSAGET(nn.Module):
             edge_logit = self.edge_head(feat).squeeze(-1)
         return node_logit, edge_logit
 
+    def score_edges(
+        self,
+        h: torch.Tensor,  # [N, hidden] — encode() output
+        edge_index: torch.Tensor,  # [2, E]
+        edge_weight: torch.Tensor | None = None,  # [E]
+        edge_ts: torch.Tensor | None = None,  # [E]
+    ) -> torch.Tensor:
+        """Inference-only edge logits [E] (same defaults as forward: weight
+        ones, ts zeros).  On a GPU in bf16 this is one fused kernel
+        (ops/hip/edge_head.hip) and the logits are fp32."""
+        from ..ops import edge_head_logits
+
+        ew = edge_weight if edge_weight is not None else torch.ones(
+            edge_index.shape[1], device=h.device, dtype=h.dtype
+        )
+        ets = edge_ts if edge_ts is not None else torch.zeros_like(ew)
+        return edge_head_logits(h, edge_index, ew, ets, self.edge_head)
+
     def num_parameters(self) -> int:
         return sum(p.numel() for p in self.parameters())

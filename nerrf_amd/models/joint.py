@@ -62,6 +62,28 @@ class NerrfJointModel(nn.Module):
             )
         return node_logit, edge_logit, seq_logit
 
+    @torch.no_grad()
+    def score(self, batch: Dict[str, torch.Tensor], edges: bool = True):
+        """Inference-only forward for serving: same outputs as forward(),
+        with the edge head through GraphSAGET.score_edges (one fused kernel
+        on a bf16 GPU model).  edges=False skips the edge head and returns
+        None in its place."""
+        gnn = self.gnn
+        h = gnn.encode(batch["x"], batch["nbr_idx"], batch["nbr_w"], batch.get("nbr_rev"))
+        node_logit = gnn.node_head(h).squeeze(-1)
+        edge_logit = None
+        edge_index = batch.get("edge_index")
+        if edges and edge_index is not None and edge_index.numel():
+            edge_logit = gnn.score_edges(
+                h, edge_index, batch.get("edge_weight"), batch.get("edge_ts")
+            )
+        seq_logit = None
+        if batch.get("seq_feats") is not None and batch["seq_feats"].shape[0] > 0:
+            seq_logit = self.lstm(
+                batch["seq_feats"], batch["seq_lengths"], batch.get("seq_plan")
+            )
+        return node_logit, edge_logit, seq_logit
+
     def loss(
         self,
         node_logit: torch.Tensor,

@@ -5,6 +5,7 @@ Ops:
   * gather_rows(h, idx[, rev])    — row gather with fast scatter backward
   * lstm_cell(xg, h, c, w_hh, b, mask) — fused LSTM recurrent step
   * lstm_sequence(...)            — whole-sequence fused LSTM (time-major)
+  * edge_head_logits(h, edge_index, ew, ets, head) — fused edge head (inference)
 
 On CPU the pure-PyTorch reference runs; on ROCm devices the in-tree HIP
 extension is mandatory (missing extension => RuntimeError, never a silent
@@ -20,7 +21,13 @@ from . import reference as _ref
 from .lstm_seq import lstm_sequence  # noqa: F401 (re-export)
 from .native import get_native, native_available  # noqa: F401 (re-export)
 
-__all__ = ["gather_mean", "lstm_cell", "lstm_sequence", "native_available"]
+__all__ = [
+    "gather_mean",
+    "lstm_cell",
+    "lstm_sequence",
+    "native_available",
+    "edge_head_logits",
+]
 
 
 class _GatherMeanFn(torch.autograd.Function):
@@ -159,6 +166,56 @@ def lstm_cell(
         m = mask.detach().contiguous().to(xg.dtype)
     return _LSTMCellFn.apply(
         xg.contiguous(), h.contiguous(), c.contiguous(), w_hh, b, m
+    )
+
+
+def _edge_head_is_fused_shape(head) -> bool:
+    """True for nn.Sequential(Linear(258, 64), GELU(erf), Linear(64, 1))."""
+    if len(head) != 3:
+        return False
+    l1, act, l2 = head[0], head[1], head[2]
+    return (
+        isinstance(l1, torch.nn.Linear)
+        and isinstance(act, torch.nn.GELU)
+        and getattr(act, "approximate", "none") == "none"
+        and isinstance(l2, torch.nn.Linear)
+        and tuple(l1.weight.shape) == (64, 258)
+        and tuple(l2.weight.shape) == (1, 64)
+        and l1.bias is not None
+        and l2.bias is not None
+    )
+
+
+def edge_head_logits(h, edge_index, edge_weight, edge_ts, head) -> torch.Tensor:
+    """Inference-only edge logits [E] for node embeddings h [N, D].
+
+    head is GraphSAGET.edge_head.  With h on a GPU, bf16, 128 wide and a
+    258 -> 64 -> 1 head, the whole edge list is one fused MFMA launch
+    (ops/hip/edge_head.hip) returning fp32; otherwise the reference math runs
+    in h's dtype.  Call under no_grad: there is no backward.
+    """
+    if not (
+        h.is_cuda
+        and h.dtype == torch.bfloat16
+        and h.dim() == 2
+        and h.shape[1] == 128
+        and _edge_head_is_fused_shape(head)
+        and head[0].weight.dtype == torch.bfloat16
+    ):
+        return _ref.edge_head_ref(h, edge_index, edge_weight, edge_ts, head)
+    ext = get_native(h)
+    w1 = head[0].weight.detach()
+    return ext.edge_head_fwd(
+        h.detach().contiguous(),
+        edge_index[0].contiguous(),
+        edge_index[1].contiguous(),
+        edge_weight.detach().to(torch.float32).contiguous(),
+        edge_ts.detach().to(torch.float32).contiguous(),
+        w1[:, :256].contiguous(),
+        w1[:, 256:258].float().contiguous(),
+        head[0].bias.detach().contiguous(),
+        head[2].weight.detach().reshape(-1).contiguous(),
+        head[2].bias.detach().contiguous(),
     )
 
 

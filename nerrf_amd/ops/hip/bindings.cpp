@@ -60,6 +60,9 @@ void launch_feature_assemble(const float*, const int*, const int*,
 void launch_sage_layer_fwd(const void*, const long*, const float*, const void*,
                            const void*, const void*, const void*, const void*,
                            void*, int, int, hipStream_t);
+void launch_edge_head_fwd(const void*, const long*, const long*, const float*,
+                          const float*, const void*, const float*, const void*,
+                          const void*, const void*, float*, long, hipStream_t);
 void launch_sage_ln_act_fwd(const void*, const void*, const void*, const void*,
                             const void*, void*, void*, float*, unsigned char*,
                             long, float, unsigned, hipStream_t);
@@ -608,6 +611,66 @@ torch::Tensor sage_layer_fwd(torch::Tensor h, torch::Tensor nbr_idx,
   return out;
 }
 
+// Fused GraphSAGE-T edge head forward (inference): gather both endpoints,
+// build [h_s*h_d, |h_s-h_d|, ew, ets], Linear(258->64) + GELU + Linear(64->1)
+// in one launch.  bf16, hidden=128, edge_head_hidden=64 only.  w1_main is
+// W1[:, :256] contiguous, w1_tail is W1[:, 256:258] in fp32.  src/dst must lie
+// in [0, N): the kernel does not check them.
+torch::Tensor edge_head_fwd(torch::Tensor h, torch::Tensor src,
+                            torch::Tensor dst, torch::Tensor ew,
+                            torch::Tensor ets, torch::Tensor w1_main,
+                            torch::Tensor w1_tail, torch::Tensor b1,
+                            torch::Tensor w2, torch::Tensor b2) {
+  const torch::Tensor* all[] = {&h, &src, &dst, &ew, &ets, &w1_main,
+                                &w1_tail, &b1, &w2, &b2};
+  const char* names[] = {"h", "src", "dst", "ew", "ets", "w1_main",
+                         "w1_tail", "b1", "w2", "b2"};
+  for (int i = 0; i < 10; ++i) {
+    check_gpu_contig(*all[i], names[i]);
+    TORCH_CHECK(all[i]->device() == h.device(), names[i],
+                " must be on the same device as h");
+  }
+  for (auto* t : {&h, &w1_main, &b1, &w2, &b2})
+    TORCH_CHECK(t->scalar_type() == torch::kBFloat16,
+                "edge_head_fwd: h, w1_main, b1, w2, b2 must be bf16");
+  TORCH_CHECK(src.scalar_type() == torch::kInt64 &&
+                  dst.scalar_type() == torch::kInt64,
+              "edge_head_fwd: src/dst must be int64");
+  TORCH_CHECK(ew.scalar_type() == torch::kFloat32 &&
+                  ets.scalar_type() == torch::kFloat32 &&
+                  w1_tail.scalar_type() == torch::kFloat32,
+              "edge_head_fwd: ew, ets, w1_tail must be fp32");
+  TORCH_CHECK(h.dim() == 2 && h.size(1) == 128,
+              "edge_head_fwd requires hidden=128 (h is [N, 128])");
+  TORCH_CHECK(w1_main.dim() == 2 && w1_main.size(0) == 64 &&
+                  w1_main.size(1) == 256 && w1_tail.dim() == 2 &&
+                  w1_tail.size(0) == 64 && w1_tail.size(1) == 2 &&
+                  b1.numel() == 64 && w2.numel() == 64 && b2.numel() == 1,
+              "edge_head_fwd requires edge_head_hidden=64: w1_main [64,256], "
+              "w1_tail [64,2], b1 [64], w2 [64], b2 [1]");
+  const long n_edges = src.numel();
+  TORCH_CHECK(src.dim() == 1 && dst.dim() == 1 && ew.dim() == 1 &&
+                  ets.dim() == 1 && dst.numel() == n_edges &&
+                  ew.numel() == n_edges && ets.numel() == n_edges,
+              "edge_head_fwd: src, dst, ew, ets must all be [E]");
+  TORCH_CHECK(n_edges == 0 || h.size(0) > 0,
+              "edge_head_fwd: edges over an empty node set");
+  check_vec_base(h, true, "h");
+  check_vec_base(w1_main, true, "w1_main");
+  auto out = torch::empty({n_edges}, h.options().dtype(torch::kFloat32));
+  if (n_edges == 0) return out;
+  auto stream = at::hip::getCurrentHIPStream();
+  nerrf::launch_edge_head_fwd(
+      h.data_ptr(), src.data_ptr<long>(), dst.data_ptr<long>(),
+      ew.data_ptr<float>(), ets.data_ptr<float>(), w1_main.data_ptr(),
+      w1_tail.data_ptr<float>(), b1.data_ptr(), w2.data_ptr(), b2.data_ptr(),
+      out.data_ptr<float>(), n_edges, stream.stream());
+  const hipError_t launch_err = hipGetLastError();
+  TORCH_CHECK(launch_err == hipSuccess, "edge_head_fwd launch failed: ",
+              hipGetErrorString(launch_err));
+  return out;
+}
+
 // Fused GraphSAGE training-layer tail: y = h + LN(dropout(GELU(zs+zn)))*g+b
 std::vector<torch::Tensor> sage_ln_act_fwd(torch::Tensor h, torch::Tensor zs,
                                            torch::Tensor zn, torch::Tensor gamma,
@@ -863,6 +926,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("sage_ln_act_bwd", &sage_ln_act_bwd, "fused GNN layer tail bwd");
   m.def("sage_layer_fwd", &sage_layer_fwd,
         "fused GraphSAGE-T layer forward (MFMA, inference)");
+  m.def("edge_head_fwd", &edge_head_fwd,
+        "fused GraphSAGE-T edge head forward (MFMA, inference) -> fp32 [E]");
   m.def("event_features", &event_features,
         "GPU delta compaction: events -> per-node feature matrix");
   m.def("mcts_search", &mcts_search, "batched root-parallel MCTS");

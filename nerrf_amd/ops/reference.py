@@ -23,6 +23,27 @@ def gather_mean_ref(
     return (gathered * wf).sum(dim=1) / denom
 
 
+def edge_head_ref(
+    h: torch.Tensor,  # [N, D]
+    edge_index: torch.Tensor,  # [2, E] int64
+    edge_weight: torch.Tensor,  # [E]
+    edge_ts: torch.Tensor,  # [E]
+    head,  # nn.Sequential(Linear(2D+2, H), GELU, Linear(H, 1))
+) -> torch.Tensor:
+    """Edge logits [E] in h's dtype: the edge branch of GraphSAGET.forward."""
+    hs, hd = h[edge_index[0]], h[edge_index[1]]
+    feat = torch.cat(
+        [
+            hs * hd,
+            (hs - hd).abs(),
+            edge_weight.unsqueeze(-1).to(h.dtype),
+            edge_ts.unsqueeze(-1).to(h.dtype),
+        ],
+        dim=-1,
+    )
+    return head(feat).squeeze(-1)
+
+
 def lstm_pointwise_fwd_ref(
     gates_pre: torch.Tensor,  # [B, 4H] pre-activation (x_t W_ih + h W_hh + b)
     c: torch.Tensor,  # [B, H]

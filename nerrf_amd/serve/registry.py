@@ -20,6 +20,7 @@ from typing import Dict, List, Optional
 
 DEFAULT_STATE_DIR = ".nerrf/detections"
 _MAX_FILE_SCORES = 200
+_LIST_TOP_EDGES = 3  # edge hits shown per detection in list() / `nerrf status`
 
 
 class DetectionRegistry:
@@ -48,6 +49,9 @@ class DetectionRegistry:
             "encrypted_paths": list(det.encrypted_paths)[:_MAX_FILE_SCORES],
             "file_scores": {p: round(float(s), 4) for p, s in top[:_MAX_FILE_SCORES]},
             "target_dir": target_dir,
+            # which process did what to which file (serve.engine.EdgeHit)
+            "top_edges": [h.as_dict() for h in det.top_edges],
+            "edge_max": float(det.edge_max),
         }
         if plan is not None:
             rec["plan"] = {
@@ -83,5 +87,6 @@ class DetectionRegistry:
                 "alarm": r.get("alarm"),
                 "target_dir": r.get("target_dir", ""),
                 "n_flagged": len(r.get("file_scores", {})),
+                "top_edges": r.get("top_edges", [])[:_LIST_TOP_EDGES],
             })
         return out

@@ -27,6 +27,7 @@ sources = [
     os.path.join(HIP_DIR, "event_scatter.hip"),
     os.path.join(HIP_DIR, "sage_fused.hip"),
     os.path.join(HIP_DIR, "sage_ln_act.hip"),
+    os.path.join(HIP_DIR, "edge_head.hip"),
 ]
 sources = [s for s in sources if os.path.exists(s)]
 
