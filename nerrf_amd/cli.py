@@ -171,7 +171,7 @@ def cmd_plan_quality(args) -> int:
 
 
 def cmd_serve(args) -> int:
-    from .serve.engine import StreamingEngine
+    from .serve.engine import StreamingEngine, culprit_brief
 
     if args.tracker:
         # live mode: consume an existing Tracker/StreamEvents endpoint and
@@ -188,7 +188,8 @@ def cmd_serve(args) -> int:
         engine = StreamingEngine(model=model, device=args.device, dtype=dtype)
         from .serve.registry import DEFAULT_STATE_DIR, DetectionRegistry
 
-        # each status line carries the top edge hit of an alarmed window
+        # each status line carries the top edge hit and the first culprit of
+        # an alarmed window
         for status in engine.run_monitor(
             interval_s=args.interval,
             max_iterations=args.iterations,
@@ -233,6 +234,8 @@ def cmd_serve(args) -> int:
                 "suspicious_files": det.encrypted_paths[:10],
                 "top_edge": (det.top_edges[0].as_dict()
                              if det.alarm and det.top_edges else None),
+                "culprit": (culprit_brief(det.culprits[0])
+                            if det.alarm and det.culprits else None),
             },
             indent=2,
         )

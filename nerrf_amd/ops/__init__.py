@@ -6,6 +6,7 @@ Ops:
   * lstm_cell(xg, h, c, w_hh, b, mask) — fused LSTM recurrent step
   * lstm_sequence(...)            — whole-sequence fused LSTM (time-major)
   * edge_head_logits(h, edge_index, ew, ets, head) — fused edge head (inference)
+  * edge_attribution(logit, edge_index, n_files, n_nodes) — per-file best edge
 
 On CPU the pure-PyTorch reference runs; on ROCm devices the in-tree HIP
 extension is mandatory (missing extension => RuntimeError, never a silent
@@ -27,6 +28,7 @@ __all__ = [
     "lstm_sequence",
     "native_available",
     "edge_head_logits",
+    "edge_attribution",
 ]
 
 
@@ -216,6 +218,41 @@ def edge_head_logits(h, edge_index, edge_weight, edge_ts, head) -> torch.Tensor:
         head[0].bias.detach().contiguous(),
         head[2].weight.detach().reshape(-1).contiguous(),
         head[2].bias.detach().contiguous(),
+    )
+
+
+def edge_attribution(
+    logit: torch.Tensor,
+    edge_index: torch.Tensor,
+    n_files: int,
+    n_nodes: int,
+    direction: str = "write",
+    thr_logit: float = 0.0,
+) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """Per file node, the process behind its highest-logit edge of one
+    direction: (culprit [F] int64 node index or -1, best_logit [F] fp32 or
+    -inf, n_hot [F] int32 = edges with logit >= thr_logit).
+
+    Nodes [0, n_files) are files, [n_files, n_nodes) processes; direction is
+    "write" (process -> file) or "read" (file -> process).  On a GPU the whole
+    edge list is reduced by two launches (ops/hip/edge_attr.hip); on the CPU
+    the reference runs.  Semantics: reference.edge_attribution_ref.
+    """
+    if direction not in ("write", "read"):
+        raise ValueError(f"direction must be 'write' or 'read', got {direction!r}")
+    ext = get_native(logit)
+    if ext is None:
+        return _ref.edge_attribution_ref(
+            logit, edge_index, n_files, n_nodes, direction, thr_logit
+        )
+    return ext.edge_attr(
+        logit.detach().to(torch.float32).contiguous(),
+        edge_index[0].contiguous(),
+        edge_index[1].contiguous(),
+        int(n_files),
+        int(n_nodes),
+        direction == "write",
+        float(thr_logit),
     )
 
 

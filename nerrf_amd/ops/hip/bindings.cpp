@@ -1,6 +1,8 @@
 // Torch extension bindings for the nerrf-amd CDNA4 kernels.
 #include <torch/extension.h>
 
+#include <limits>
+
 #include <ATen/hip/HIPContext.h>
 #include <hip/hip_runtime.h>
 
@@ -63,6 +65,9 @@ void launch_sage_layer_fwd(const void*, const long*, const float*, const void*,
 void launch_edge_head_fwd(const void*, const long*, const long*, const float*,
                           const float*, const void*, const float*, const void*,
                           const void*, const void*, float*, long, hipStream_t);
+void launch_edge_attr(const float*, const long*, const long*,
+                      unsigned long long*, int*, long*, float*, long, long,
+                      long, bool, float, hipStream_t);
 void launch_sage_ln_act_fwd(const void*, const void*, const void*, const void*,
                             const void*, void*, void*, float*, unsigned char*,
                             long, float, unsigned, hipStream_t);
@@ -671,6 +676,63 @@ torch::Tensor edge_head_fwd(torch::Tensor h, torch::Tensor src,
   return out;
 }
 
+// Per-file edge attribution: for each file node, the process whose wanted-
+// direction edge (write: proc -> file, read: file -> proc) has the highest
+// logit, that logit, and the count of such edges with logit >= thr_logit.
+// Nodes [0, n_files) are files, [n_files, n_nodes) processes.  Edges with an
+// endpoint outside [0, n_nodes) are skipped by the kernel, not read through.
+// Returns (culprit [n_files] int64, -1 = none; best_logit [n_files] fp32,
+// -inf = none; n_hot [n_files] int32).  No host synchronisation.
+std::vector<torch::Tensor> edge_attr(torch::Tensor logit, torch::Tensor src,
+                                     torch::Tensor dst, long n_files,
+                                     long n_nodes, bool want_write,
+                                     double thr_logit) {
+  const torch::Tensor* all[] = {&logit, &src, &dst};
+  const char* names[] = {"logit", "src", "dst"};
+  for (int i = 0; i < 3; ++i) {
+    check_gpu_contig(*all[i], names[i]);
+    TORCH_CHECK(all[i]->device() == logit.device(), names[i],
+                " must be on the same device as logit");
+  }
+  TORCH_CHECK(logit.scalar_type() == torch::kFloat32,
+              "edge_attr: logit must be fp32");
+  TORCH_CHECK(src.scalar_type() == torch::kInt64 &&
+                  dst.scalar_type() == torch::kInt64,
+              "edge_attr: src/dst must be int64");
+  const long n_edges = logit.numel();
+  TORCH_CHECK(logit.dim() == 1 && src.dim() == 1 && dst.dim() == 1 &&
+                  src.numel() == n_edges && dst.numel() == n_edges,
+              "edge_attr: logit, src, dst must all be [E]");
+  TORCH_CHECK(n_files >= 0 && n_files <= n_nodes,
+              "edge_attr: need 0 <= n_files <= n_nodes, got n_files=", n_files,
+              " n_nodes=", n_nodes);
+  TORCH_CHECK(n_nodes - n_files < (1L << 32),
+              "edge_attr: at most 2^32 - 1 process nodes");
+  auto opts = logit.options();
+  auto n_hot = torch::zeros({n_files}, opts.dtype(torch::kInt32));
+  if (n_edges == 0 || n_files == 0) {
+    return {torch::full({n_files}, -1L, opts.dtype(torch::kInt64)),
+            torch::full({n_files}, -std::numeric_limits<float>::infinity(),
+                        opts.dtype(torch::kFloat32)),
+            n_hot};
+  }
+  // packed (orderable logit, inverted process index) keys; zero = no edge
+  auto best = torch::zeros({n_files}, opts.dtype(torch::kInt64));
+  auto culprit = torch::empty({n_files}, opts.dtype(torch::kInt64));
+  auto best_logit = torch::empty({n_files}, opts.dtype(torch::kFloat32));
+  auto stream = at::hip::getCurrentHIPStream();
+  nerrf::launch_edge_attr(
+      logit.data_ptr<float>(), src.data_ptr<long>(), dst.data_ptr<long>(),
+      reinterpret_cast<unsigned long long*>(best.data_ptr<long>()),
+      n_hot.data_ptr<int>(), culprit.data_ptr<long>(),
+      best_logit.data_ptr<float>(), n_edges, n_files, n_nodes, want_write,
+      static_cast<float>(thr_logit), stream.stream());
+  const hipError_t launch_err = hipGetLastError();
+  TORCH_CHECK(launch_err == hipSuccess, "edge_attr launch failed: ",
+              hipGetErrorString(launch_err));
+  return {culprit, best_logit, n_hot};
+}
+
 // Fused GraphSAGE training-layer tail: y = h + LN(dropout(GELU(zs+zn)))*g+b
 std::vector<torch::Tensor> sage_ln_act_fwd(torch::Tensor h, torch::Tensor zs,
                                            torch::Tensor zn, torch::Tensor gamma,
@@ -928,6 +990,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "fused GraphSAGE-T layer forward (MFMA, inference)");
   m.def("edge_head_fwd", &edge_head_fwd,
         "fused GraphSAGE-T edge head forward (MFMA, inference) -> fp32 [E]");
+  m.def("edge_attr", &edge_attr,
+        "per-file best edge: (culprit [F] int64, best_logit [F] fp32, "
+        "n_hot [F] int32)");
   m.def("event_features", &event_features,
         "GPU delta compaction: events -> per-node feature matrix");
   m.def("mcts_search", &mcts_search, "batched root-parallel MCTS");

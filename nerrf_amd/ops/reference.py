@@ -44,6 +44,55 @@ def edge_head_ref(
     return head(feat).squeeze(-1)
 
 
+def edge_attribution_ref(
+    logit: torch.Tensor,  # [E]
+    edge_index: torch.Tensor,  # [2, E] int64
+    n_files: int,
+    n_nodes: int,
+    direction: str = "write",
+    thr_logit: float = 0.0,
+) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """Per file node, the best edge of one direction: (culprit [F] int64,
+    best_logit [F] fp32, n_hot [F] int32).
+
+    Nodes [0, n_files) are files, [n_files, n_nodes) processes.  A "write"
+    edge runs process -> file, a "read" edge file -> process.  culprit is the
+    process node index of the highest-logit edge (ties: lowest index), -1 and
+    -inf where a file has no such edge; n_hot counts the file's edges with
+    logit >= thr_logit (compared in fp32).  Edges with an endpoint outside
+    [0, n_nodes), between two files or two processes, of the other direction
+    or with a NaN logit are skipped; -0.0 counts as +0.0.
+    """
+    if direction not in ("write", "read"):
+        raise ValueError(f"direction must be 'write' or 'read', got {direction!r}")
+    n_files, n_nodes = int(n_files), int(n_nodes)
+    dev = logit.device
+    v = logit.detach().float().reshape(-1) + 0.0  # -0.0 -> +0.0
+    src, dst = edge_index[0].reshape(-1), edge_index[1].reshape(-1)
+    ok = (src >= 0) & (src < n_nodes) & (dst >= 0) & (dst < n_nodes)
+    s_file, d_file = src < n_files, dst < n_files
+    if direction == "write":
+        ok = ok & ~s_file & d_file
+        f, p = dst, src
+    else:
+        ok = ok & s_file & ~d_file
+        f, p = src, dst
+    ok = ok & ~torch.isnan(v)
+    f, p, v = f[ok], p[ok], v[ok]
+    best = torch.full((n_files,), float("-inf"), device=dev, dtype=torch.float32)
+    best = best.scatter_reduce(0, f, v, "amax", include_self=True)
+    # lowest process index among the edges that equal their file's maximum
+    win = v == best[f]
+    none = torch.iinfo(torch.int64).max
+    culprit = torch.full((n_files,), none, device=dev, dtype=torch.int64)
+    culprit = culprit.scatter_reduce(0, f[win], p[win], "amin", include_self=True)
+    culprit = torch.where(culprit == none, torch.full_like(culprit, -1), culprit)
+    hot = v >= torch.tensor(thr_logit, dtype=torch.float32, device=dev)
+    n_hot = torch.zeros(n_files, device=dev, dtype=torch.int32)
+    n_hot.index_add_(0, f[hot], torch.ones_like(f[hot], dtype=torch.int32))
+    return culprit, best, n_hot
+
+
 def lstm_pointwise_fwd_ref(
     gates_pre: torch.Tensor,  # [B, 4H] pre-activation (x_t W_ih + h W_hh + b)
     c: torch.Tensor,  # [B, H]

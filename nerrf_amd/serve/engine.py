@@ -14,11 +14,12 @@ it.
 """
 from __future__ import annotations
 
+import math
 import os
 import re
 import time
 from dataclasses import dataclass, field
-from typing import Dict, List, Optional
+from typing import Dict, List, Optional, Tuple
 
 import numpy as np
 import torch
@@ -50,6 +51,50 @@ class EdgeHit:
 
 
 @dataclass
+class Culprit:
+    """One process and the hot files attributed to it."""
+
+    proc: int  # process key, as in Detection.proc_scores
+    score: float  # best attribution score over its files
+    n_files: int
+    mb: float  # window bytes of its files (Detection.file_mb), in MB
+    files: List[str]  # score descending, then path
+
+    def as_dict(self) -> dict:
+        return {"proc": int(self.proc), "score": float(self.score),
+                "n_files": int(self.n_files), "mb": float(self.mb),
+                "files": list(self.files)}
+
+
+def build_culprits(file_culprit: Dict[str, Tuple[int, float]],
+                   file_mb: Dict[str, float]) -> List[Culprit]:
+    """Roll a path -> (process, score) map up per process: most files first,
+    then best score, then process key."""
+    by_proc: Dict[int, List[Tuple[str, float]]] = {}
+    for path, (proc, score) in file_culprit.items():
+        by_proc.setdefault(proc, []).append((path, score))
+    out = []
+    for proc, items in by_proc.items():
+        items.sort(key=lambda ps: (-ps[1], ps[0]))
+        out.append(Culprit(
+            proc=proc,
+            score=items[0][1],
+            n_files=len(items),
+            mb=float(sum(file_mb.get(p, 0.0) for p, _ in items)),
+            files=[p for p, _ in items],
+        ))
+    out.sort(key=lambda c: (-c.n_files, -c.score, c.proc))
+    return out
+
+
+def culprit_brief(c: Culprit) -> dict:
+    """A culprit without its file list (status lines)."""
+    d = c.as_dict()
+    del d["files"]
+    return d
+
+
+@dataclass
 class Detection:
     alarm: bool
     t_detect: float
@@ -72,6 +117,14 @@ class Detection:
     # edge scores do not feed the alarm rule
     top_edges: List[EdgeHit] = field(default_factory=list)
     edge_max: float = 0.0
+    # per-file attribution over the whole edge list (not bounded by
+    # top_edges): live path -> (process key, sigmoid of its best write-edge
+    # logit), for the files whose best write edge reaches the engine's
+    # attribute_threshold; the same rolled up per process; and the hot files
+    # that two or more processes hot-wrote, where naming one is a judgement
+    file_culprit: Dict[str, Tuple[int, float]] = field(default_factory=dict)
+    culprits: List[Culprit] = field(default_factory=list)
+    contested: List[str] = field(default_factory=list)
 
 
 PRETRAINED_DIR = "checkpoints/pretrained"
@@ -114,9 +167,20 @@ class StreamingEngine:
         calibration: Optional[str] = "auto",
         content_probe_root: Optional[str] = None,
         top_edges: int = 32,
+        attribute: bool = True,
+        attribute_threshold: float = 0.5,
     ) -> None:
         if top_edges < 0:
             raise ValueError(f"top_edges must be >= 0, got {top_edges}")
+        if not 0.0 < attribute_threshold < 1.0:
+            raise ValueError(
+                f"attribute_threshold must lie in (0, 1), got {attribute_threshold}")
+        # attribute every hot file to the process behind its best write edge;
+        # runs on the edge head's logits, so top_edges=0 turns it off too
+        self.attribute = bool(attribute)
+        self.attribute_threshold = float(attribute_threshold)
+        self._attribute_thr_logit = math.log(
+            self.attribute_threshold / (1.0 - self.attribute_threshold))
         # how many of the window's highest-scoring edges a Detection names;
         # 0 skips the edge head altogether
         self.top_edges = int(top_edges)
@@ -297,6 +361,23 @@ class StreamingEngine:
                 batch["edge_index"][:, top_i].cpu().numpy(),
                 batch["edge_weight"][top_i].float().cpu().numpy(),
             )
+        # per-file attribution over the full edge list, reduced on the device;
+        # only the hot files' rows cross to the host
+        attr_hot = None
+        if self.attribute and edge_logit is not None and edge_logit.numel():
+            from ..ops import edge_attribution
+
+            a_proc, a_logit, a_nhot = edge_attribution(
+                edge_logit, batch["edge_index"], int(parts["n_files"]),
+                int(parts["n_nodes"]), "write", self._attribute_thr_logit,
+            )
+            hot_f = torch.nonzero(a_nhot > 0).squeeze(1)
+            attr_hot = (
+                hot_f.cpu().numpy(),
+                a_proc[hot_f].cpu().numpy(),
+                torch.sigmoid(a_logit[hot_f]).cpu().numpy(),
+                a_nhot[hot_f].cpu().numpy(),
+            )
         node_score = torch.sigmoid(node_logit.float()).cpu().numpy()
         if timing is not None:
             timing["model_fwd_sync"] = time.perf_counter() - _t0 - sum(timing.values())
@@ -338,6 +419,16 @@ class StreamingEngine:
                     weight=w_,
                 ))
         edge_max = top_hits[0].score if top_hits else 0.0
+        # hot files -> culprit process, through the same key mapping
+        file_culprit: Dict[str, Tuple[int, float]] = {}
+        contested: List[str] = []
+        if attr_hot is not None:
+            for f_, p_, sc_, nh_ in zip(*(a.tolist() for a in attr_hot)):
+                path = strings[int(node_key[f_])]
+                file_culprit[path] = (int(node_key[p_]), sc_)
+                if nh_ >= 2:
+                    contested.append(path)
+            contested.sort()
         file_mb: Dict[str, float] = {}
         if seq_score is not None and len(seq_score) == len(seq_fids):
             for pid_, sc in zip(seq_fids.tolist(), seq_score.tolist()):
@@ -485,22 +576,37 @@ class StreamingEngine:
             seq_max=seq_max,
             top_edges=top_hits,
             edge_max=edge_max,
+            file_culprit=file_culprit,
+            culprits=build_culprits(file_culprit, file_mb),
+            contested=contested,
         )
 
 
     # -------------------------------------------------------------------- plan
     def plan(self, det: Detection, n_sims: int = 1024, use_gpu: Optional[bool] = None,
              model_refine: bool = True, planner: str = "mcts",
-             max_plans: Optional[int] = None) -> PlanResult:
+             max_plans: Optional[int] = None,
+             culprit: Optional[int] = None) -> PlanResult:
         """planner="mcts" (default) searches with `n_sims` simulations;
         planner="exact" enumerates every plan (planner/oracle.py) and raises
-        ValueError when the plan space exceeds `max_plans`."""
+        ValueError when the plan space exceeds `max_plans`.
+
+        `culprit` (a process key of det.proc_scores) plans against that one
+        process: only the files det.file_culprit attributes to it, and its own
+        node score; ValueError when no file is attributed to it."""
         if planner not in ("mcts", "exact"):
             raise ValueError(f"unknown planner {planner!r}: expected 'mcts' or 'exact'")
-        paths = list(det.file_scores.keys())
+        if culprit is None:
+            paths = list(det.file_scores.keys())
+            proc = max(det.proc_scores.values(), default=0.0)
+        else:
+            paths = [p for p in det.file_scores
+                     if p in det.file_culprit and det.file_culprit[p][0] == culprit]
+            if not paths:
+                raise ValueError(f"no file is attributed to process {culprit!r}")
+            proc = det.proc_scores.get(culprit, 0.0)
         scores = np.array([det.file_scores[p] for p in paths], dtype=np.float64)
         mb = np.array([max(det.file_mb.get(p, 0.01), 0.01) for p in paths], dtype=np.float64)
-        proc = max(det.proc_scores.values(), default=0.0)
         if det.encrypted_paths:
             proc = max(proc, 0.9)
         clean_mb = float(sum(det.file_mb.values()))
@@ -624,6 +730,8 @@ class StreamingEngine:
             "indicators": det.indicators,
             "window_events": det.window_events,
             "top_edges": det.top_edges,
+            "file_culprit": det.file_culprit,
+            "contested": det.contested,
         }
         gathered: list = [None] * world
         dist.all_gather_object(gathered, payload, group=group)
@@ -654,6 +762,14 @@ class StreamingEngine:
         hits = [h for g in gathered for h in g["top_edges"]]
         merged.top_edges = sorted(hits, key=lambda h: -h.score)[: self.top_edges]
         merged.edge_max = merged.top_edges[0].score if merged.top_edges else 0.0
+        # per path the stronger attribution wins; culprits are rebuilt from
+        # the merged map against the merged byte counts
+        for g in gathered:
+            for p, (proc, s) in g["file_culprit"].items():
+                if p not in merged.file_culprit or s > merged.file_culprit[p][1]:
+                    merged.file_culprit[p] = (proc, s)
+        merged.contested = sorted({p for g in gathered for p in g["contested"]})
+        merged.culprits = build_culprits(merged.file_culprit, merged.file_mb)
         return merged
 
     # ----------------------------------------------------------------- monitor
@@ -714,6 +830,9 @@ class StreamingEngine:
                 # which process did what to which file, on alarm
                 "top_edge": (det.top_edges[0].as_dict()
                              if det.alarm and det.top_edges else None),
+                # the process most hot files are attributed to, on alarm
+                "culprit": (culprit_brief(det.culprits[0])
+                            if det.alarm and det.culprits else None),
             }
             yield status
             it += 1

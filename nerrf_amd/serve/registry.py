@@ -52,6 +52,13 @@ class DetectionRegistry:
             # which process did what to which file (serve.engine.EdgeHit)
             "top_edges": [h.as_dict() for h in det.top_edges],
             "edge_max": float(det.edge_max),
+            # hot files rolled up per culprit process (serve.engine.Culprit),
+            # and the hot files more than one process hot-wrote
+            "culprits": [
+                dict(c.as_dict(), files=c.files[:_MAX_FILE_SCORES])
+                for c in det.culprits
+            ],
+            "contested": list(det.contested),
         }
         if plan is not None:
             rec["plan"] = {
@@ -88,5 +95,9 @@ class DetectionRegistry:
                 "target_dir": r.get("target_dir", ""),
                 "n_flagged": len(r.get("file_scores", {})),
                 "top_edges": r.get("top_edges", [])[:_LIST_TOP_EDGES],
+                "culprits": [
+                    {"proc": c["proc"], "n_files": c["n_files"], "score": c["score"]}
+                    for c in r.get("culprits", [])
+                ],
             })
         return out

@@ -28,6 +28,7 @@ sources = [
     os.path.join(HIP_DIR, "sage_fused.hip"),
     os.path.join(HIP_DIR, "sage_ln_act.hip"),
     os.path.join(HIP_DIR, "edge_head.hip"),
+    os.path.join(HIP_DIR, "edge_attr.hip"),
 ]
 sources = [s for s in sources if os.path.exists(s)]
 
