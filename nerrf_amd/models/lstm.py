@@ -14,9 +14,13 @@ rows: sequences are sorted by length once per batch (`SeqPlan`, built on the
 host with the batch or from `lengths`), every LSTM tensor holds only the
 sum(lengths) live (timestep, sequence) rows, and the recurrence runs
 max(lengths) steps through `lstm_bilayer2_packed`.  NERRF_LSTM_PACKED=0
-(docs/flags.md) selects the dense path there too.  Inference keeps the whole
-batch dense with masked state updates (`lstm_bilayer2`, the rec-fused step
-kernel).
+(docs/flags.md) selects the dense path there too.  Inference on a GPU in
+bf16 at the spec shape (hidden 256, 2 layers, 16 input features) runs over
+the same packed layout through `lstm_bilayer2_packed_infer`: one fused
+row-count step kernel, a C++ step loop per direction, and no layer-1
+projection slab (NERRF_LSTM_PACKED_INFER=0 turns it off).  Every other
+inference keeps the whole batch dense with masked state updates
+(`lstm_bilayer2`, the rec-fused step kernel).
 """
 from __future__ import annotations
 
@@ -30,9 +34,11 @@ import torch.nn as nn
 from ..ops import lstm_sequence
 from ..ops.lstm_seq import (
     SeqPlan,
+    build_infer_plan,
     build_seq_plan,
     lstm_bilayer2,
     lstm_bilayer2_packed,
+    lstm_bilayer2_packed_infer,
 )
 
 
@@ -103,14 +109,22 @@ class BiLSTMDetector(nn.Module):
 
         `plan` (optional): the `SeqPlan` of `lengths`, e.g. the one
         `WindowBatch.to_torch` builds on the host; without it the packed
-        path builds one from `lengths` with one device-to-host copy."""
-        packed = (
-            os.environ.get("NERRF_LSTM_PACKED", "1") == "1"
-            and torch.is_grad_enabled()
-            and any(p.requires_grad for p in self.parameters())
-        )
-        if packed:
+        paths build one from `lengths` with one device-to-host copy."""
+        train = torch.is_grad_enabled() and any(
+            p.requires_grad for p in self.parameters())
+        if train and os.environ.get("NERRF_LSTM_PACKED", "1") == "1":
             return self._forward_packed(feats, lengths, plan)
+        c = self.cfg
+        if (
+            not train
+            and not (torch.is_grad_enabled() and feats.requires_grad)
+            and feats.is_cuda
+            and feats.dtype == torch.bfloat16
+            and (c.hidden, c.layers, c.in_dim) == (256, 2, 16)
+            and feats.is_contiguous()
+            and os.environ.get("NERRF_LSTM_PACKED_INFER", "1") != "0"
+        ):
+            return self._forward_packed_infer(feats, lengths, plan)
         return self._forward_dense(feats, lengths)
 
     def _forward_packed(self, feats, lengths, plan) -> torch.Tensor:
@@ -140,9 +154,38 @@ class BiLSTMDetector(nn.Module):
             fin = fin * plan.live.to(fin.dtype)
         return self.head(fin).squeeze(-1)
 
+    @torch.no_grad()
+    def _forward_packed_infer(self, feats, lengths, plan) -> torch.Tensor:
+        """Serving path (bf16 on a GPU, spec shape): the packed layout of
+        `_forward_packed` through the fused row-count step kernel.  Layer 1
+        projects x_t inside the kernel straight from the padded `feats`, so
+        no [N, E] gather and no layer-1 projection exist; layer 2 projects
+        the packed layer-1 output with one GEMM over the N live rows."""
+        b, t, _ = feats.shape
+        hid = self.cfg.hidden
+        if plan is None:
+            ln = lengths.detach().cpu() if isinstance(lengths, torch.Tensor) else lengths
+            plan = build_infer_plan(ln, t, feats.device)
+        assert plan.n_seq == b and plan.t_max == t, "plan does not match feats"
+        n = plan.n_rows
+        if n == 0:  # every sequence is empty: zero final states
+            return self.head(feats.new_zeros(b, 2 * hid)).squeeze(-1)
+        (f1, r1), (f2, r2) = self.dirs[0], self.dirs[1]
+        h = lstm_bilayer2_packed_infer(
+            plan, f1.w_hh, f1.b, r1.w_hh, r1.b,
+            feats=feats, w_ih_f=f1.w_ih, w_ih_b=r1.w_ih,
+        )
+        xg2p = torch.matmul(h, torch.cat([f2.w_ih, r2.w_ih], dim=0).t())  # [N, 2*4H]
+        h = lstm_bilayer2_packed_infer(plan, f2.w_hh, f2.b, r2.w_hh, r2.b, xg2p=xg2p)
+        fin = h.reshape(2 * n, hid).index_select(0, plan.fin_idx).view(b, 2 * hid)
+        if plan.has_empty:
+            fin = fin * plan.live.to(fin.dtype)
+        return self.head(fin).squeeze(-1)
+
     def _forward_dense(self, feats: torch.Tensor, lengths: torch.Tensor) -> torch.Tensor:
-        """Dense masked path over all B x T positions: inference (the
-        rec-fused step kernel) and NERRF_LSTM_PACKED=0."""
+        """Dense masked path over all B x T positions: inference outside the
+        packed-inference contract (the rec-fused step kernel),
+        NERRF_LSTM_PACKED=0 and NERRF_LSTM_PACKED_INFER=0."""
         b, t, _ = feats.shape
         ar = torch.arange(t, device=feats.device)
         mask = (ar.unsqueeze(1) < lengths.unsqueeze(0)).to(feats.dtype)  # [T, B]

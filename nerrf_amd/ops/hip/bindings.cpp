@@ -42,6 +42,10 @@ void launch_lstm_rec_fwd(const void*, const void*, const void*, const void*,
 void launch_lstm_rec_bwd(const void*, const void*, const void*, const void*,
                          const void*, const void*, const float*, void*, void*,
                          void*, int, long, long, hipStream_t);
+void launch_lstm_packed_dir(void*, const void*, const void*, const void*,
+                            void*, const void*, const int*, const void*, int,
+                            int, const long*, const long*, int, bool, long,
+                            long, hipStream_t);
 void launch_rec_gemm_fwd(const void*, const void*, void*, long, long, long,
                          hipStream_t);
 void launch_rec_gemm_dgrad(const void*, const void*, const void*, void*,
@@ -361,6 +365,101 @@ void lstm_rec_fwd(torch::Tensor h_prev, torch::Tensor w_hh, torch::Tensor xg,
       c_prev.data_ptr(), mask_ptr, h_out.data_ptr(), c_out.data_ptr(),
       want_gates ? gates_act.data_ptr() : nullptr, (int)batch, hprev_stride,
       xg_stride, hout_stride, stream.stream());
+}
+
+// Packed BiLSTM inference, one direction of one layer (bf16, H == 256): all
+// live timesteps of the length-sorted packed layout (SeqPlan) as one call —
+// the step loop runs here on the current stream, one fused launch per step
+// (lstm_rec_packed.hip).
+//   h_dir  [N, 256]  this direction's column slab of the packed [N, 2H] layer
+//                    output (rows strided); every slab is written, the
+//                    previous step's slab is the next step's h input
+//   c      [>= n_0, 256]  cell state, updated in place; need not be initialised
+//   xg_dir [N, 1024] this direction's slab of the packed projection (layer 2),
+//                    or empty: then feats [B, T, 16], perm [>= n_0] int32 and
+//                    w_ih [1024, 16] are the layer-1 inputs and the kernel
+//                    projects x_t itself
+//   batch_sizes [t_live] non-increasing n_t, offsets [t_live + 1] their
+//                    running sum from 0 (host lists)
+void lstm_packed_infer_dir(torch::Tensor h_dir, torch::Tensor w_hh,
+                           torch::Tensor bias, torch::Tensor c,
+                           torch::Tensor xg_dir, torch::Tensor feats,
+                           torch::Tensor perm, torch::Tensor w_ih,
+                           std::vector<long> batch_sizes,
+                           std::vector<long> offsets, bool reverse) {
+  const long h_stride = row_stride_checked(h_dir, "h_dir");
+  check_gpu_contig(w_hh, "w_hh");
+  check_gpu_contig(bias, "bias");
+  check_gpu_contig(c, "c");
+  const bool xproj = xg_dir.numel() == 0;
+  for (auto* t : {&h_dir, &w_hh, &bias, &c}) {
+    TORCH_CHECK(t->scalar_type() == torch::kBFloat16,
+                "lstm_packed_infer_dir is bf16-only");
+  }
+  TORCH_CHECK(h_dir.size(1) == 256 && w_hh.dim() == 2 && w_hh.size(0) == 1024 &&
+                  w_hh.size(1) == 256 && bias.numel() == 1024 && c.dim() == 2 &&
+                  c.size(1) == 256,
+              "lstm_packed_infer_dir requires H=256");
+  const long t_live = (long)batch_sizes.size();
+  TORCH_CHECK((long)offsets.size() == t_live + 1 && offsets[0] == 0,
+              "offsets must be [t_live + 1] and start at 0");
+  for (long t = 0; t < t_live; ++t) {
+    TORCH_CHECK(batch_sizes[t] >= 0 &&
+                    (t == 0 || batch_sizes[t] <= batch_sizes[t - 1]) &&
+                    offsets[t + 1] == offsets[t] + batch_sizes[t],
+                "batch_sizes must be non-increasing and offsets their running sum");
+  }
+  const long n0 = t_live ? batch_sizes[0] : 0;
+  TORCH_CHECK(n0 <= std::numeric_limits<int>::max(), "too many sequences");
+  TORCH_CHECK(offsets.back() <= h_dir.size(0),
+              "offsets exceed the rows of the output");
+  TORCH_CHECK(c.size(0) >= n0, "c must cover batch_sizes[0] rows");
+  // 16-byte accesses: row slices start at row offsets, so strides and bases
+  TORCH_CHECK(h_stride % 8 == 0, "h_dir rows must be 16-byte aligned");
+  check_vec_base(h_dir, true, "h_dir");
+  check_vec_base(w_hh, true, "w_hh");
+  check_vec_base(bias, true, "bias");
+  check_vec_base(c, true, "c");
+  long xg_stride = 0;
+  int t_max = 0, n_seq = 0;
+  if (xproj) {
+    check_gpu_contig(feats, "feats");
+    check_gpu_contig(perm, "perm");
+    check_gpu_contig(w_ih, "w_ih");
+    TORCH_CHECK(feats.scalar_type() == torch::kBFloat16 &&
+                    w_ih.scalar_type() == torch::kBFloat16,
+                "lstm_packed_infer_dir is bf16-only");
+    TORCH_CHECK(perm.scalar_type() == torch::kInt32, "perm must be int32");
+    TORCH_CHECK(feats.dim() == 3 && feats.size(2) == 16 && w_ih.dim() == 2 &&
+                    w_ih.size(0) == 1024 && w_ih.size(1) == 16,
+                "the in-kernel projection requires in_dim=16");
+    TORCH_CHECK(perm.numel() >= n0, "perm must cover batch_sizes[0] rows");
+    TORCH_CHECK(t_live <= feats.size(1), "more steps than feats has timesteps");
+    TORCH_CHECK(feats.size(0) <= std::numeric_limits<int>::max() &&
+                    feats.size(1) <= std::numeric_limits<int>::max(),
+                "feats too large");
+    check_vec_base(feats, true, "feats");
+    check_vec_base(w_ih, true, "w_ih");
+    t_max = (int)feats.size(1);
+    n_seq = (int)feats.size(0);
+  } else {
+    xg_stride = row_stride_checked(xg_dir, "xg_dir");
+    TORCH_CHECK(xg_dir.scalar_type() == torch::kBFloat16,
+                "lstm_packed_infer_dir is bf16-only");
+    TORCH_CHECK(xg_dir.size(1) == 1024 && xg_dir.size(0) >= offsets.back(),
+                "xg_dir must be [N, 1024]");
+    TORCH_CHECK(xg_stride % 8 == 0, "xg_dir rows must be 16-byte aligned");
+    check_vec_base(xg_dir, true, "xg_dir");
+  }
+  if (offsets.back() == 0) return;
+  auto stream = at::hip::getCurrentHIPStream();
+  nerrf::launch_lstm_packed_dir(
+      h_dir.data_ptr(), w_hh.data_ptr(), xproj ? nullptr : xg_dir.data_ptr(),
+      bias.data_ptr(), c.data_ptr(), xproj ? feats.data_ptr() : nullptr,
+      xproj ? perm.data_ptr<int>() : nullptr,
+      xproj ? w_ih.data_ptr() : nullptr, t_max, n_seq, batch_sizes.data(),
+      offsets.data(), (int)t_live, reverse, h_stride, xg_stride,
+      stream.stream());
 }
 
 // Fused recurrent backward (bf16, H == 256): gate grads + grad_c_prev +
@@ -1013,6 +1112,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("prev_rows") = -1);
   m.def("lstm_rec_fwd", &lstm_rec_fwd,
         "fused recurrent GEMM + LSTM pointwise fwd (bf16, H=256)");
+  m.def("lstm_packed_infer_dir", &lstm_packed_infer_dir,
+        "packed BiLSTM inference, one direction of one layer: C++ step loop "
+        "over the fused row-count kernel (bf16, H=256)",
+        py::arg("h_dir"), py::arg("w_hh"), py::arg("bias"), py::arg("c"),
+        py::arg("xg_dir"), py::arg("feats"), py::arg("perm"), py::arg("w_ih"),
+        py::arg("batch_sizes"), py::arg("offsets"), py::arg("reverse"));
   m.def("lstm_rec_bwd", &lstm_rec_bwd,
         "fused LSTM gate grads + grad_h GEMM bwd (bf16, H=256)");
   m.def("rec_gemm_fwd", &rec_gemm_fwd,

@@ -41,10 +41,18 @@ over a length-sorted packed layout (`SeqPlan`): every LSTM tensor holds only
 the N = sum(lengths) live (timestep, sequence) rows, and both directions loop
 over max(lengths) steps instead of T.  The dense masked ops above compute,
 store and read back a row for every padded position (62.6 % of the rows of
-the benchmark batch) and stay for inference and for A/B runs
-(NERRF_LSTM_PACKED=0, read by the model).  The packed path has no mask: the
-pointwise kernels take row counts instead (`prev_rows`, `in_rows`), so a
-step may cover more rows than its predecessor produced without a zero-fill.
+the benchmark batch) and stay for A/B runs (NERRF_LSTM_PACKED=0,
+NERRF_LSTM_PACKED_INFER=0, read by the model) and for inference outside the
+packed kernel's contract.  The packed path has no mask: the pointwise
+kernels take row counts instead (`prev_rows`, `in_rows`), so a step may
+cover more rows than its predecessor produced without a zero-fill.
+
+`lstm_bilayer2_packed_infer` is the inference layer op over the same layout
+(bf16, H = 256): one extension call per direction runs the whole step loop
+in C++ over the fused row-count kernel of lstm_rec_packed.hip — cell state
+in place, no c history, no gate store, and for layer 1 no input-projection
+slab either (the kernel projects x_t from `feats` through `perm`).  Its plan
+(`build_infer_plan`) has no N-sized index arrays.
 """
 from __future__ import annotations
 
@@ -548,6 +556,9 @@ class SeqPlan:
     fin_idx: torch.Tensor      # [2B] rows of the [2N, H] view holding each
     #                            sequence's final fwd / bwd state
     live: torch.Tensor         # [B, 1] f32, 0 where length == 0
+    perm_dev: Optional[torch.Tensor] = None  # [B] int32 perm on the device
+    #                            (inference plans: the layer-1 kernel gathers
+    #                            feats rows through it)
 
     def to(self, device) -> "SeqPlan":
         """The same plan with its index tensors on `device` (host fields
@@ -560,6 +571,8 @@ class SeqPlan:
             k: getattr(self, k).to(device, non_blocking=True)
             for k in ("pack_idx", "hin_idx", "fin_idx", "live")
         }
+        if self.perm_dev is not None:
+            moved["perm_dev"] = self.perm_dev.to(device, non_blocking=True)
         return dataclasses.replace(self, **moved)
 
     @property
@@ -587,10 +600,9 @@ class SeqPlan:
         ]
 
 
-def build_seq_plan(lengths, t_max: int, device="cpu") -> SeqPlan:
-    """Plan from `lengths` ([B]; numpy array or tensor — a device tensor
-    costs one device-to-host copy here).  Lengths are clamped to
-    [0, t_max]."""
+def _plan_host(lengths, t_max: int):
+    """The O(B + T) part of a plan: (ln, perm, inv_perm, n_t, off, fin_idx,
+    live) as numpy arrays, lengths clamped to [0, t_max]."""
     if isinstance(lengths, torch.Tensor):
         lengths = lengths.detach().cpu().numpy()
     ln = np.clip(np.asarray(lengths).astype(np.int64).reshape(-1), 0, int(t_max))
@@ -603,6 +615,24 @@ def build_seq_plan(lengths, t_max: int, device="cpu") -> SeqPlan:
     n_t = b - np.cumsum(np.bincount(ln, minlength=t_live + 1))[:t_live]
     off = np.zeros(t_live + 1, dtype=np.int64)
     np.cumsum(n_t, out=off[1:])
+    # final states per sequence, in the original order
+    live = ln > 0
+    fin_f = np.where(live, off[np.maximum(ln - 1, 0)] + inv_perm, 0)
+    fin_b = np.where(live, inv_perm, 0)
+    fin_idx = np.stack([2 * fin_f, 2 * fin_b + 1], axis=1).reshape(-1)
+    return ln, perm, inv_perm, n_t, off, fin_idx, live
+
+
+def _plan_dev(a, device, dt=torch.int64):
+    return torch.from_numpy(np.ascontiguousarray(a)).to(dt).to(device, non_blocking=True)
+
+
+def build_seq_plan(lengths, t_max: int, device="cpu") -> SeqPlan:
+    """Plan from `lengths` ([B]; numpy array or tensor — a device tensor
+    costs one device-to-host copy here).  Lengths are clamped to
+    [0, t_max]."""
+    ln, perm, inv_perm, n_t, off, fin_idx, live = _plan_host(lengths, t_max)
+    b, t_live = int(ln.shape[0]), int(n_t.shape[0])
     n_rows = int(off[-1])
 
     t_of = np.repeat(np.arange(t_live, dtype=np.int64), n_t)  # [N]
@@ -615,22 +645,32 @@ def build_seq_plan(lengths, t_max: int, device="cpu") -> SeqPlan:
     n_next = np.append(n_t, 0)[t_of + 1] if t_live else n_t
     src_b = np.where(r_of < n_next, off[np.minimum(t_of + 1, t_live)] + r_of, n_rows)
     hin_idx = np.stack([2 * src_f, 2 * src_b + 1], axis=1).reshape(-1)
-    # final states per sequence, in the original order
-    r_seq = inv_perm
-    live = ln > 0
-    fin_f = np.where(live, off[np.maximum(ln - 1, 0)] + r_seq, 0)
-    fin_b = np.where(live, r_seq, 0)
-    fin_idx = np.stack([2 * fin_f, 2 * fin_b + 1], axis=1).reshape(-1)
-
-    def dev(a, dt=torch.int64):
-        return torch.from_numpy(np.ascontiguousarray(a)).to(dt).to(device, non_blocking=True)
 
     return SeqPlan(
         n_seq=b, t_max=int(t_max), perm=perm, inv_perm=inv_perm,
         batch_sizes=[int(x) for x in n_t], offsets=[int(x) for x in off],
         has_empty=bool((~live).any()),
-        pack_idx=dev(pack_idx), hin_idx=dev(hin_idx), fin_idx=dev(fin_idx),
-        live=dev(live.reshape(b, 1), torch.float32),
+        pack_idx=_plan_dev(pack_idx, device), hin_idx=_plan_dev(hin_idx, device),
+        fin_idx=_plan_dev(fin_idx, device),
+        live=_plan_dev(live.reshape(b, 1), device, torch.float32),
+    )
+
+
+def build_infer_plan(lengths, t_max: int, device="cpu") -> SeqPlan:
+    """Inference plan from host `lengths`: what `lstm_bilayer2_packed_infer`
+    and the final-state gather need — perm (also as an int32 device tensor),
+    batch_sizes, offsets, fin_idx, live, has_empty.  pack_idx and hin_idx are
+    empty, so it is built in O(B + T) with no N-sized array."""
+    ln, perm, inv_perm, n_t, off, fin_idx, live = _plan_host(lengths, t_max)
+    b = int(ln.shape[0])
+    none = torch.empty(0, dtype=torch.int64, device=device)
+    return SeqPlan(
+        n_seq=b, t_max=int(t_max), perm=perm, inv_perm=inv_perm,
+        batch_sizes=[int(x) for x in n_t], offsets=[int(x) for x in off],
+        has_empty=bool((~live).any()),
+        pack_idx=none, hin_idx=none, fin_idx=_plan_dev(fin_idx, device),
+        live=_plan_dev(live.reshape(b, 1), device, torch.float32),
+        perm_dev=_plan_dev(perm, device, torch.int32),
     )
 
 
@@ -832,3 +872,93 @@ def lstm_bilayer2_packed(
     assert xg2p.shape[0] == plan.n_rows, "xg2p does not match the plan"
     infer = _infer_mode(xg2p, w_f, b_f, w_b, b_b)
     return _LSTMBiLayer2PackedFn.apply(xg2p, w_f, b_f, w_b, b_b, plan, infer)
+
+
+def _packed_infer_native(dt, w_f, w_b, xg2p, feats, w_ih_f, w_ih_b) -> bool:
+    """Shape contract of lstm_rec_packed.hip: bf16, H = 256, contiguous
+    weights, and for the in-kernel projection contiguous [B, T, 16] feats."""
+    if not (_mfma_eligible(dt, w_f.shape[1], w_f) and w_b.is_contiguous()):
+        return False
+    if xg2p is not None:
+        return xg2p.shape[1] == 2048 and xg2p.stride(0) % 8 == 0
+    return (
+        feats.shape[2] == 16 and feats.is_contiguous()
+        and w_ih_f.is_contiguous() and w_ih_b.is_contiguous()
+    )
+
+
+def lstm_bilayer2_packed_infer(
+    plan: SeqPlan,
+    w_f: torch.Tensor,
+    b_f: torch.Tensor,
+    w_b: torch.Tensor,
+    b_b: torch.Tensor,
+    *,
+    xg2p: Optional[torch.Tensor] = None,   # [N, 2*4H] packed projection, or
+    feats: Optional[torch.Tensor] = None,  # [B, T, E] padded layer-1 input
+    w_ih_f: Optional[torch.Tensor] = None,  # [4H, E] with feats
+    w_ih_b: Optional[torch.Tensor] = None,
+) -> torch.Tensor:
+    """Inference-only `lstm_bilayer2_packed` -> [N, 2H].  The input is
+    either the packed projection `xg2p` (layer 2) or the padded `feats` with
+    the two input weights (layer 1).  On a GPU inside the kernel's contract
+    (bf16, H = 256, E = 16) each direction is one extension call that loops
+    over the live steps in C++ (lstm_rec_packed.hip); layer 1 then builds no
+    projection at all.  Everywhere else layer 1 gathers and projects the
+    live rows here and the layer runs through `lstm_bilayer2_packed`."""
+    if (xg2p is None) == (feats is None):
+        raise ValueError("pass exactly one of xg2p and feats")
+    if feats is not None and (w_ih_f is None or w_ih_b is None):
+        raise ValueError("feats needs w_ih_f and w_ih_b")
+    tensors = [x for x in (w_f, b_f, w_b, b_b, xg2p, feats, w_ih_f, w_ih_b)
+               if x is not None]
+    if not _infer_mode(*tensors):
+        raise RuntimeError(
+            "lstm_bilayer2_packed_infer is inference-only: an input requires "
+            "grad and grad mode is on (use lstm_bilayer2_packed)"
+        )
+    src = xg2p if xg2p is not None else feats
+    dev, dt = src.device, src.dtype
+    hdim = w_f.shape[1]
+    n_rows = plan.n_rows
+    if xg2p is not None:
+        assert xg2p.dim() == 2 and xg2p.stride(1) == 1, "xg2p rows must be contiguous"
+        assert xg2p.shape[0] == n_rows, "xg2p does not match the plan"
+    else:
+        assert feats.shape[0] == plan.n_seq and feats.shape[1] == plan.t_max, \
+            "feats does not match the plan"
+    ext = get_native(src)
+    if ext is None or n_rows == 0 or not _packed_infer_native(
+            dt, w_f, w_b, xg2p, feats, w_ih_f, w_ih_b):
+        with torch.no_grad():
+            if xg2p is None:
+                pack_idx = np.concatenate([
+                    plan.perm[:n] * plan.t_max + t
+                    for t, n in enumerate(plan.batch_sizes)
+                ]) if n_rows else np.zeros(0, dtype=np.int64)
+                rows = feats.reshape(plan.n_seq * plan.t_max, -1).index_select(
+                    0, _plan_dev(pack_idx, dev))
+                xg2p = torch.matmul(rows, torch.cat([w_ih_f, w_ih_b], dim=0).t())
+            return lstm_bilayer2_packed(xg2p, plan, w_f, b_f, w_b, b_b)
+    h2p = torch.empty(n_rows, 2 * hdim, device=dev, dtype=dt)
+    c = torch.empty(plan.batch_sizes[0], hdim, device=dev, dtype=dt)
+    none = torch.empty(0, device=dev, dtype=dt)
+    gdim = 4 * hdim
+    if xg2p is None:  # a full plan (build_seq_plan) carries no device perm
+        perm = plan.perm_dev
+        if perm is None or perm.device != dev:
+            perm = _plan_dev(plan.perm, dev, torch.int32)
+    for rev, w_hh, bias, w_ih in ((False, w_f, b_f, w_ih_f), (True, w_b, b_b, w_ih_b)):
+        h_dir = h2p[:, rev * hdim:(rev + 1) * hdim]
+        if xg2p is None:
+            ext.lstm_packed_infer_dir(
+                h_dir, w_hh, bias.contiguous(), c, none, feats, perm, w_ih,
+                plan.batch_sizes, plan.offsets, rev,
+            )
+        else:
+            ext.lstm_packed_infer_dir(
+                h_dir, w_hh, bias.contiguous(), c,
+                xg2p[:, rev * gdim:(rev + 1) * gdim], none, none, none,
+                plan.batch_sizes, plan.offsets, rev,
+            )
+    return h2p

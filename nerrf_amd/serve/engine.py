@@ -347,6 +347,14 @@ class StreamingEngine:
             "seq_feats": seq_feats.to(self.device),
             "seq_lengths": seq_lengths.to(self.device),
         }
+        if self.device.type == "cuda":
+            # length-sort plan of the packed BiLSTM inference path, built on
+            # the host from the lengths already here: no device-to-host copy
+            from ..ops.lstm_seq import build_infer_plan
+
+            batch["seq_plan"] = build_infer_plan(
+                seq_lengths_cpu, seq_feats.shape[1], self.device
+            )
         node_logit, edge_logit, seq_logit = self.model.score(
             batch, edges=self.top_edges > 0
         )

@@ -20,6 +20,7 @@ sources = [
     os.path.join(HIP_DIR, "lstm_cell.hip"),
     os.path.join(HIP_DIR, "lstm_step_fused.hip"),
     os.path.join(HIP_DIR, "lstm_rec_fused.hip"),
+    os.path.join(HIP_DIR, "lstm_rec_packed.hip"),
     os.path.join(HIP_DIR, "stream_gemm.hip"),
     os.path.join(HIP_DIR, "rec_gemm.hip"),
     os.path.join(HIP_DIR, "mcts.hip"),
