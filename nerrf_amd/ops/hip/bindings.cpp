@@ -15,6 +15,14 @@ void launch_mcts(const float*, const float*, const float*, float, float,
 void launch_eval_plans(const float*, const float*, const float*, float, float,
                        const PlannerParamsDev&, const int*, int, int, float*,
                        hipStream_t);
+hipError_t launch_mcts_multi(const float*, const float*, const float*, float,
+                             const MultiPlannerParamsDev&, int, int, int, int*,
+                             float*, hipStream_t);
+hipError_t launch_mcts_multi_eval_plans(const float*, const float*,
+                                        const float*, float,
+                                        const MultiPlannerParamsDev&,
+                                        const int*, int, int, float*,
+                                        hipStream_t);
 void launch_plan_oracle(const float*, const float*, const float*, const float*,
                         const float*, const PlannerParamsDev&, int, int, int,
                         float*, int*, unsigned*, hipStream_t);
@@ -945,6 +953,101 @@ torch::Tensor mcts_eval_plans(torch::Tensor gscore, torch::Tensor gmb,
   return out;
 }
 
+// ---- joint planner over P processes (mcts_multi.hip) ----
+// Bad arguments raise ValueError (TORCH_CHECK_VALUE) before anything launches.
+nerrf::MultiPlannerParamsDev multi_params_from_dict(
+    const pybind11::dict& d, const torch::Tensor& gscore,
+    const torch::Tensor& gmb, const torch::Tensor& gfiles,
+    const torch::Tensor& proc_scores) {
+  const long g = gscore.numel(), np = proc_scores.numel();
+  TORCH_CHECK_VALUE(g >= 1 && g <= 16, "joint planner: 1 <= G <= 16 (got ", g, ")");
+  TORCH_CHECK_VALUE(np >= 1 && np <= NERRF_MULTI_MAX_PROCS,
+                    "joint planner: 1 <= P <= 8 (got ", np, ")");
+  TORCH_CHECK_VALUE(d["n_groups"].cast<long>() == g,
+                    "joint planner: params n_groups != len(gscore)");
+  TORCH_CHECK_VALUE(d["max_depth"].cast<long>() >= 0 &&
+                        d["max_depth"].cast<long>() <= 16,
+                    "joint planner: 0 <= max_depth <= 16");
+  for (const torch::Tensor* t : {&gscore, &gmb, &gfiles}) {
+    TORCH_CHECK_VALUE(t->is_cuda() && t->is_contiguous() && t->dim() == 1 &&
+                          t->numel() == g &&
+                          t->scalar_type() == torch::kFloat32,
+                      "joint planner: group tensors must be contiguous f32 [G] "
+                      "on the GPU");
+  }
+  TORCH_CHECK_VALUE(!proc_scores.is_cuda() && proc_scores.is_contiguous() &&
+                        proc_scores.dim() == 1 &&
+                        proc_scores.scalar_type() == torch::kFloat32,
+                    "joint planner: proc_scores must be a contiguous f32 [P] "
+                    "CPU tensor (it travels in the kernel arguments)");
+  nerrf::MultiPlannerParamsDev mp;
+  mp.base = params_from_dict(d);
+  mp.n_procs = (int)np;
+  mp.base.n_actions = mp.n_procs + 2 + mp.base.n_groups;
+  for (int q = 0; q < NERRF_MULTI_MAX_PROCS; ++q)
+    mp.proc_score[q] = q < np ? proc_scores.data_ptr<float>()[q] : 0.0f;
+  return mp;
+}
+
+std::vector<torch::Tensor> mcts_multi_search(
+    torch::Tensor gscore, torch::Tensor gmb, torch::Tensor gfiles,
+    torch::Tensor proc_scores, double remaining_clean_mb,
+    pybind11::dict param_dict, long n_trees) {
+  auto mp = multi_params_from_dict(param_dict, gscore, gmb, gfiles, proc_scores);
+  const auto& p = mp.base;
+  TORCH_CHECK_VALUE(p.sims_per_tree >= 1, "joint planner: sims_per_tree >= 1");
+  TORCH_CHECK_VALUE(n_trees >= 1 && n_trees <= (1L << 24),
+                    "joint planner: 1 <= n_trees <= 2^24");
+  const long cap = (long)p.sims_per_tree * p.max_depth + 2;
+  const long tree_bytes = nerrf::mcts_multi_tree_bytes(cap, p.n_actions);
+  TORCH_CHECK_VALUE(cap < 32768 && tree_bytes <= NERRF_MULTI_MAX_TREE_BYTES,
+                    "joint planner: one tree of ", cap, " nodes x ",
+                    p.n_actions, " actions takes ", tree_bytes,
+                    " bytes and must fit in ", NERRF_MULTI_MAX_TREE_BYTES,
+                    " bytes of LDS; lower sims_per_tree or max_depth");
+  auto root_visits = torch::empty({n_trees, (long)p.n_actions},
+                                  gscore.options().dtype(torch::kInt32));
+  auto root_value = torch::empty({n_trees, (long)p.n_actions},
+                                 gscore.options().dtype(torch::kFloat32));
+  auto stream = at::hip::getCurrentHIPStream();
+  const hipError_t err = nerrf::launch_mcts_multi(
+      gscore.data_ptr<float>(), gmb.data_ptr<float>(), gfiles.data_ptr<float>(),
+      (float)remaining_clean_mb, mp, (int)n_trees, (int)cap, (int)tree_bytes,
+      root_visits.data_ptr<int>(), root_value.data_ptr<float>(),
+      stream.stream());
+  TORCH_CHECK(err == hipSuccess, "mcts_multi launch failed: ",
+              hipGetErrorString(err));
+  return {root_visits, root_value};
+}
+
+torch::Tensor mcts_multi_eval_plans(torch::Tensor gscore, torch::Tensor gmb,
+                                    torch::Tensor gfiles,
+                                    torch::Tensor proc_scores,
+                                    double remaining_clean_mb,
+                                    pybind11::dict param_dict,
+                                    torch::Tensor plans) {
+  auto mp = multi_params_from_dict(param_dict, gscore, gmb, gfiles, proc_scores);
+  TORCH_CHECK_VALUE(plans.is_cuda() && plans.is_contiguous() &&
+                        plans.dim() == 2 &&
+                        plans.scalar_type() == torch::kInt32 &&
+                        plans.get_device() == gscore.get_device(),
+                    "joint planner: plans must be contiguous i32 [n, L] on "
+                    "the group tensors' GPU");
+  const long n_plans = plans.size(0), plan_len = plans.size(1);
+  TORCH_CHECK_VALUE(n_plans <= (1L << 30) && plan_len <= (1L << 16),
+                    "joint planner: too many plans");
+  auto out = torch::empty({n_plans}, gscore.options().dtype(torch::kFloat32));
+  if (n_plans == 0) return out;
+  auto stream = at::hip::getCurrentHIPStream();
+  const hipError_t err = nerrf::launch_mcts_multi_eval_plans(
+      gscore.data_ptr<float>(), gmb.data_ptr<float>(), gfiles.data_ptr<float>(),
+      (float)remaining_clean_mb, mp, plans.data_ptr<int>(), (int)n_plans,
+      (int)plan_len, out.data_ptr<float>(), stream.stream());
+  TORCH_CHECK(err == hipSuccess, "mcts_multi_eval_plans launch failed: ",
+              hipGetErrorString(err));
+  return out;
+}
+
 // Exhaustive plan oracle over a batch of S states (plan_oracle.hip).
 // Returns CPU tensors, one row per state and one slot per first action
 // (slot 0 = STOP, the empty plan; slot a = best plan starting with action a):
@@ -1096,6 +1199,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "GPU delta compaction: events -> per-node feature matrix");
   m.def("mcts_search", &mcts_search, "batched root-parallel MCTS");
   m.def("mcts_eval_plans", &mcts_eval_plans, "batch plan reward evaluation");
+  m.def("mcts_multi_search", &mcts_multi_search,
+        "joint P-process MCTS: per-tree root visits and values");
+  m.def("mcts_multi_eval_plans", &mcts_multi_eval_plans,
+        "batch plan reward evaluation of the P-process MDP");
   m.def("plan_oracle_search", &plan_oracle_search,
         "exhaustive best plan per first action over a batch of states",
         pybind11::arg("gscore"), pybind11::arg("gmb"), pybind11::arg("gfiles"),

@@ -13,6 +13,10 @@ plans (G=8, D=10: 9 864 101).  `exhaustive_best_cpu` enumerates them with
 runs the batched HIP search (ops/hip/plan_oracle.hip) and re-scores the
 per-first-action winners in fp64.
 
+A `MultiPlannerState` (P processes, rewards.simulate_plan_multi) has
+n = P + 1 + G non-STOP actions and the same canonical form; its oracle runs
+on the CPU only.
+
 Tie-break (shared by both paths): among plans of equal reward the shorter plan
 wins, then the lexicographically smaller action tuple.
 """
@@ -23,7 +27,8 @@ from typing import Dict, List, Optional, Sequence, Tuple, Union
 
 import numpy as np
 
-from .rewards import A_STOP, PlannerParams, PlannerState, simulate_plan
+from .rewards import (A_STOP, MultiPlannerState, PlannerParams, PlannerState,
+                      plan_reward, simulate_plan)
 
 # Default cap of the CPU reference.  simulate_plan costs about 10 us per plan
 # in CPython on one core (13 700 plans: ~0.12 s), so 1e6 plans return in
@@ -104,7 +109,8 @@ def _check_state(state: PlannerState, params: PlannerParams) -> None:
     if state.n_groups < 1 or any(len(a) != state.n_groups for a in arrs):
         raise ValueError("planner state needs >= 1 group and equal-length group arrays")
     vals = np.concatenate([np.asarray(a, dtype=np.float64).ravel() for a in arrs]
-                          + [np.array([state.proc_score, state.remaining_clean_mb], dtype=np.float64)])
+                          + [np.atleast_1d(np.asarray(state.proc_score, dtype=np.float64)),
+                             np.array([state.remaining_clean_mb], dtype=np.float64)])
     if not np.all(np.isfinite(vals)):
         raise ValueError("planner state holds non-finite values")
     pvals = [params.downtime_weight, params.revert_time_s, params.kill_time_s,
@@ -135,13 +141,13 @@ def exhaustive_best_cpu(
     (about 10 us per plan)."""
     params = params or PlannerParams()
     _check_state(state, params)
-    n = 2 + state.n_groups
+    n = state.n_actions - 1
     n_plans = count_plans(n, params.max_depth)
     if n_plans > max_plans:
         raise _too_many(state, params, n_plans, max_plans)
     depth_lim = min(n, max(int(params.max_depth), 0))
     fab: Dict[int, Tuple[float, List[int]]] = {
-        A_STOP: (float(simulate_plan(state, [A_STOP], params)), [])
+        A_STOP: (float(plan_reward(state, [A_STOP], params)), [])
     }
     actions = list(range(1, n + 1))
     plan: List[int] = []
@@ -150,7 +156,7 @@ def exhaustive_best_cpu(
     def rec() -> None:
         # plans arrive in lexicographic preorder, so a tie between equal
         # lengths keeps the earlier plan
-        r = float(simulate_plan(state, plan, params))
+        r = float(plan_reward(state, plan, params))
         cur = fab.get(plan[0])
         if cur is None or r > cur[0] or (r == cur[0] and len(plan) < len(cur[1])):
             fab[plan[0]] = (r, list(plan))
@@ -256,16 +262,18 @@ def exhaustive_best(
     count exceeds `max_plans` and on non-finite inputs.  `prefix_len`
     overrides the GPU work decomposition (0 = automatic)."""
     params = params or PlannerParams()
-    single = isinstance(state_or_states, PlannerState)
+    single = isinstance(state_or_states, (PlannerState, MultiPlannerState))
     states = [state_or_states] if single else list(state_or_states)
     if not states:
         return []
     for st in states:
         _check_state(st, params)
-        n_plans = count_plans(2 + st.n_groups, params.max_depth)
+        n_plans = count_plans(st.n_actions - 1, params.max_depth)
         if n_plans > max_plans:
             raise _too_many(st, params, n_plans, max_plans)
     dev = str(device)
+    if dev != "cpu" and any(isinstance(st, MultiPlannerState) for st in states):
+        raise ValueError("the plan oracle of a MultiPlannerState runs on device='cpu' only")
     if dev == "cpu" or params.max_depth < 1:
         res = [exhaustive_best_cpu(st, params, max_plans=min(max_plans, CPU_MAX_PLANS)) for st in states]
     else:
@@ -290,7 +298,7 @@ def plan_regret(
     params = params or PlannerParams()
     if oracle is None:
         oracle = exhaustive_best(state, params, device=device)
-    return float(oracle.reward - simulate_plan(state, list(plan) + [A_STOP], params))
+    return float(oracle.reward - plan_reward(state, list(plan) + [A_STOP], params))
 
 
 def reward_tol(reward: float) -> float:

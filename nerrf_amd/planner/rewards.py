@@ -18,7 +18,7 @@ planner maximises  -(E[data_loss_MB] + 0.1 * downtime_s + fp_penalty_MB).
 from __future__ import annotations
 
 from dataclasses import dataclass
-from typing import List
+from typing import List, Optional
 
 import numpy as np
 
@@ -59,6 +59,10 @@ class PlannerState:
     @property
     def n_groups(self) -> int:
         return int(len(self.group_score))
+
+    @property
+    def n_actions(self) -> int:
+        return 3 + self.n_groups  # STOP, KILL, RESTORE, revert g
 
 
 def build_state(
@@ -147,3 +151,120 @@ def simulate_plan(
         + staleness
     )
     return -(loss + params.downtime_weight * downtime + params.fp_weight * fp_mb)
+
+
+# ---- joint plan over P processes (ops/hip/mcts_multi.hip) ----
+#
+# action ids: 0 STOP | 1 + p KILL process p | P + 1 RESTORE | P + 2 + g REVERT g
+# (P = 1 is the numbering above)
+MAX_PROCS = 8
+MAX_GROUPS = 16
+
+
+@dataclass
+class MultiPlannerState:
+    """PlannerState with P attack processes instead of one."""
+
+    group_score: np.ndarray  # [G]
+    group_mb: np.ndarray  # [G]
+    group_files: np.ndarray  # [G]
+    proc_score: np.ndarray  # [P] anomaly score per process
+    remaining_clean_mb: float
+    # [G] process index each group's files are attributed to: bookkeeping for
+    # the engine and describe_multi, never read by the reward
+    group_owner: Optional[np.ndarray] = None
+
+    def __post_init__(self) -> None:
+        self.proc_score = np.atleast_1d(np.asarray(self.proc_score, dtype=np.float64))
+        if not 1 <= len(self.proc_score) <= MAX_PROCS:
+            raise ValueError(f"a joint plan covers 1..{MAX_PROCS} processes (got {len(self.proc_score)})")
+        if len(self.group_score) > MAX_GROUPS:
+            raise ValueError(f"a joint plan covers at most {MAX_GROUPS} groups (got {len(self.group_score)})")
+
+    @property
+    def n_groups(self) -> int:
+        return int(len(self.group_score))
+
+    @property
+    def n_procs(self) -> int:
+        return int(len(self.proc_score))
+
+    @property
+    def n_actions(self) -> int:
+        return self.n_procs + 2 + self.n_groups
+
+
+def simulate_plan_multi(
+    state: MultiPlannerState,
+    actions: List[int],
+    params: PlannerParams,
+) -> float:
+    """`simulate_plan` with P processes: each KILL stops one of them, and what
+    the attack adds while we act scales with `live`, the summed score of the
+    processes still alive.
+
+    Mirrors `eval_plan_multi` in ops/hip/mcts_multi.hip.  `live` is summed in
+    ascending p from zero after every KILL (never decremented), so host and
+    device add in one order.  For P = 1 the value equals `simulate_plan`'s.
+    """
+    g = state.n_groups
+    n_procs = state.n_procs
+    a_restore = n_procs + 1
+    unrec = state.group_score * state.group_mb
+    reverted = np.zeros(g, dtype=np.float64)
+    fp_mb = 0.0
+    downtime = 0.0
+    alive = [True] * n_procs
+    live = 0.0
+    for p in range(n_procs):
+        live += float(state.proc_score[p])
+    restored = False
+    staleness = 0.0
+    ongoing = 0.0
+    for a in actions:
+        if a == A_STOP:
+            break
+        if 1 <= a <= n_procs:
+            if alive[a - 1]:
+                downtime += params.kill_time_s
+                alive[a - 1] = False
+                live = 0.0
+                for p in range(n_procs):
+                    if alive[p]:
+                        live += float(state.proc_score[p])
+            continue
+        if a == a_restore:
+            if restored:
+                continue
+            dt = params.restore_time_s
+            ongoing += params.attack_rate_mbps * dt * live
+            downtime += dt
+            reverted[:] = 1.0
+            staleness = params.restore_loss_mb
+            restored = True
+            continue
+        gi = a - (n_procs + 2)
+        if gi < 0 or gi >= g or reverted[gi] > 0:
+            continue  # invalid / duplicate: no-op
+        dt = params.revert_time_s * max(state.group_files[gi], 1.0)
+        ongoing += params.attack_rate_mbps * dt * live
+        downtime += dt
+        reverted[gi] = 1.0
+        fp_mb += (1.0 - state.group_score[gi]) * state.group_mb[gi] * 0.05
+    if any(alive):
+        ongoing += params.attack_rate_mbps * params.horizon_s * live
+        downtime += params.horizon_s * live
+    loss = (
+        float(((1.0 - reverted) * unrec).sum())
+        + min(ongoing, state.remaining_clean_mb)
+        + staleness
+    )
+    return -(loss + params.downtime_weight * downtime + params.fp_weight * fp_mb)
+
+
+def plan_reward(state, actions: List[int], params: PlannerParams) -> float:
+    """The state's own reward: `simulate_plan_multi` for a MultiPlannerState,
+    `simulate_plan` otherwise."""
+    if isinstance(state, MultiPlannerState):
+        return simulate_plan_multi(state, actions, params)
+    return simulate_plan(state, actions, params)

@@ -27,8 +27,10 @@ import torch
 from ..data.trace import EventArray
 from ..graph.store import DeltaGraphStore
 from ..models.joint import JointConfig, NerrfJointModel
-from ..planner.mcts import PlanResult, run_mcts, run_mcts_gpu
-from ..planner.rewards import PlannerParams, build_state
+from ..planner.mcts import (PlanResult, run_mcts, run_mcts_gpu, run_mcts_multi,
+                            run_mcts_multi_gpu)
+from ..planner.rewards import (MAX_GROUPS, MAX_PROCS, MultiPlannerState,
+                               PlannerParams, build_state)
 from .rollback import RollbackResult, execute_rollback
 
 _SUSPICIOUS_EXT = re.compile(r"\.(lockbit\w*|encrypted|locked|crypt\w*)$", re.IGNORECASE)
@@ -125,6 +127,20 @@ class Detection:
     file_culprit: Dict[str, Tuple[int, float]] = field(default_factory=dict)
     culprits: List[Culprit] = field(default_factory=list)
     contested: List[str] = field(default_factory=list)
+
+
+@dataclass
+class JointPlanResult(PlanResult):
+    """One plan against several culprits (StreamingEngine.plan_joint).  Action
+    ids are those of rewards.simulate_plan_multi with P = len(proc_keys)."""
+
+    proc_keys: List[int] = field(default_factory=list)  # KILL p stops proc_keys[p]
+    group_owner: List[int] = field(default_factory=list)  # [G] index into proc_keys
+    group_paths: List[List[str]] = field(default_factory=list)  # [G] files REVERT g reverts
+    unplanned: List[str] = field(default_factory=list)  # scored files of no chosen culprit
+
+    def describe(self, n_groups: Optional[int] = None) -> List[str]:
+        return self.describe_multi(len(self.proc_keys), self.proc_keys)
 
 
 PRETRAINED_DIR = "checkpoints/pretrained"
@@ -631,6 +647,63 @@ class StreamingEngine:
         if model_refine and det.refine_ctx is not None and paths:
             res = self._refine_plan(res, det, state, paths, scores)
         return res
+
+    def plan_joint(self, det: Detection, culprits: Optional[List[int]] = None,
+                   n_sims: int = 1024, use_gpu: Optional[bool] = None) -> JointPlanResult:
+        """One plan against several culprits at once: one KILL per process,
+        RESTORE, the damage cap and the depth budget shared between them.
+
+        `culprits` are process keys (default: those of det.culprits, in their
+        order, at most 8).  Each one's attributed files are bucketed by score
+        as in build_state into its share of planner_params.n_groups; files of
+        no chosen culprit are not planned over and come back as `unplanned`.
+        ValueError when no chosen culprit has an attributed file."""
+        if culprits is None:
+            keys = [c.proc for c in det.culprits][:MAX_PROCS]
+        else:
+            keys = list(dict.fromkeys(int(k) for k in culprits))
+            if len(keys) > MAX_PROCS:
+                raise ValueError(f"a joint plan covers at most {MAX_PROCS} culprits (got {len(keys)})")
+        per_proc = max(1, min(self.planner_params.n_groups, MAX_GROUPS) // max(len(keys), 1))
+        clean_mb = float(sum(det.file_mb.values()))
+        gs, gm, gf, owner, group_paths = [], [], [], [], []
+        for pi, key in enumerate(keys):
+            paths = [p for p in det.file_scores
+                     if p in det.file_culprit and det.file_culprit[p][0] == key]
+            if not paths:
+                continue
+            scores = np.array([det.file_scores[p] for p in paths], dtype=np.float64)
+            mb = np.array([max(det.file_mb.get(p, 0.01), 0.01) for p in paths], dtype=np.float64)
+            part = build_state(scores, mb, proc_score=0.0, remaining_clean_mb=clean_mb,
+                               n_groups=per_proc)
+            split = np.array_split(np.argsort(-scores, kind="stable"), per_proc)
+            for g, ids in enumerate(split):  # build_state's buckets; empty ones drop out
+                if len(ids):
+                    gs.append(part.group_score[g])
+                    gm.append(part.group_mb[g])
+                    gf.append(part.group_files[g])
+                    owner.append(pi)
+                    group_paths.append([paths[i] for i in ids])
+        if not group_paths:
+            raise ValueError(f"no file is attributed to any of the processes {keys!r}")
+        proc = [det.proc_scores.get(k, 0.0) for k in keys]
+        if det.encrypted_paths:
+            proc = [max(s, 0.9) for s in proc]
+        state = MultiPlannerState(
+            group_score=np.array(gs, dtype=np.float64), group_mb=np.array(gm, dtype=np.float64),
+            group_files=np.array(gf, dtype=np.float64), proc_score=np.array(proc, dtype=np.float64),
+            remaining_clean_mb=clean_mb, group_owner=np.array(owner, dtype=np.int64))
+        if use_gpu is None:
+            use_gpu = self.device.type == "cuda"
+        if use_gpu:
+            res = run_mcts_multi_gpu(state, self.planner_params, n_sims=n_sims, device=str(self.device))
+        else:
+            res = run_mcts_multi(state, self.planner_params, n_sims=n_sims)
+        planned = {p for ps in group_paths for p in ps}
+        return JointPlanResult(
+            plan=res.plan, ranked_actions=res.ranked_actions, root_value=res.root_value,
+            simulations=res.simulations, proc_keys=keys, group_owner=owner,
+            group_paths=group_paths, unplanned=[p for p in det.file_scores if p not in planned])
 
     def _plan_exact(self, state, use_gpu: bool, max_plans: Optional[int]) -> PlanResult:
         """Exhaustive planner: the oracle's plan, with the exact root action
