@@ -12,6 +12,7 @@ Commands (spec: reference ROADMAP.md:86, README.md:82 — `nerrf undo`,
   nerrf train ...                    training entrypoint (= ai/train.py)
   nerrf serve --trace T              tracker-sim + streaming engine demo
   nerrf plan-quality --states N      MCTS regret against the exhaustive plan oracle
+                                     (--procs P: the joint planner and oracle)
 
 Entry point: `python -m nerrf_amd.cli <cmd>` (also installed as ./nerrf).
 """
@@ -165,7 +166,8 @@ def cmd_plan_quality(args) -> int:
     params = PlannerParams(n_groups=groups, max_depth=depth)
     sims = [int(x) for x in args.sims.split(",") if x]
     report = measure_plan_quality(args.states, args.seed, sims=sims,
-                                  device=args.device, params=params)
+                                  device=args.device, params=params,
+                                  n_procs=args.procs)
     print(json.dumps(report, indent=2))
     return 0
 
@@ -334,6 +336,9 @@ def build_parser() -> argparse.ArgumentParser:
                    help="file groups G (default 8; 4 on cpu)")
     p.add_argument("--max-depth", type=int, default=None,
                    help="plan depth D (default 10; 6 on cpu)")
+    p.add_argument("--procs", type=int, default=1,
+                   help="culprit processes P; above 1 measures the joint planner "
+                        "against the joint oracle")
 
     p = sub.add_parser("serve", help="streaming engine (live tracker or trace demo)")
     p.add_argument("--trace", default=None, help="trace file (demo mode)")

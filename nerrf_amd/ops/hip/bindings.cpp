@@ -26,6 +26,10 @@ hipError_t launch_mcts_multi_eval_plans(const float*, const float*,
 void launch_plan_oracle(const float*, const float*, const float*, const float*,
                         const float*, const PlannerParamsDev&, int, int, int,
                         float*, int*, unsigned*, hipStream_t);
+hipError_t launch_plan_oracle_multi(const float*, const float*, const float*,
+                                    const float*, const float*,
+                                    const PlannerParamsDev&, int, int, int,
+                                    int, float*, int*, unsigned*, hipStream_t);
 void launch_gather_mean_fwd(const void*, const long*, const float*, void*, int,
                             int, int, bool, hipStream_t);
 void launch_gather_mean_bwd(const void*, const long*, const float*, float*,
@@ -1048,6 +1052,58 @@ torch::Tensor mcts_multi_eval_plans(torch::Tensor gscore, torch::Tensor gmb,
   return out;
 }
 
+// Host reduction shared by the two plan oracles: per state, the best work
+// item under each first action (reward, then shorter; items are in
+// lexicographic prefix order, so an equal (reward, len) keeps the earlier one),
+// unpacked into  len i32 [S, n+1]  and  plan i32 [S, n+1, 16]  (STOP-padded;
+// slot 0 stays the empty plan).  Not hot.
+std::pair<torch::Tensor, torch::Tensor> reduce_oracle_winners(
+    const torch::Tensor& item_reward, const torch::Tensor& item_len,
+    const torch::Tensor& item_plan, int n, int L, int depth_lim) {
+  const long S = item_reward.size(0), n_prefix = item_reward.size(1);
+  auto h_reward = item_reward.cpu();
+  auto h_len = item_len.cpu();
+  auto h_plan = item_plan.cpu();
+  const float* hr = h_reward.data_ptr<float>();
+  const int* hl = h_len.data_ptr<int>();
+  const unsigned* hp = reinterpret_cast<const unsigned*>(h_plan.data_ptr<int>());
+  auto cpu_i = torch::TensorOptions().dtype(torch::kInt32);
+  auto win_len = torch::zeros({S, (long)n + 1}, cpu_i);
+  auto win_plan = torch::zeros({S, (long)n + 1, 16}, cpu_i);
+  int* wl = win_len.data_ptr<int>();
+  int* wp = win_plan.data_ptr<int>();
+  auto field = [](const unsigned* w, int i) {
+    return (int)((w[i / 6] >> (5 * (i % 6))) & 31u);
+  };
+  for (long s = 0; s < S; ++s) {
+    std::vector<long> best(n + 1, -1);
+    for (long i = 0; i < n_prefix; ++i) {
+      const long o = s * n_prefix + i;
+      const int len = hl[o];
+      TORCH_CHECK(len >= 1 && len <= depth_lim,
+                  "plan oracle: no finite reward under a prefix "
+                  "(non-finite planner inputs?)");
+      const int a0 = field(hp + o * 6, 0);
+      TORCH_CHECK(a0 >= 1 && a0 <= n, "plan oracle: corrupt winner");
+      const long b = best[a0];
+      if (b < 0 || hr[o] > hr[b] || (hr[o] == hr[b] && len < hl[b])) best[a0] = o;
+    }
+    for (int a = 1; a <= n; ++a) {
+      const long o = best[a];
+      TORCH_CHECK(o >= 0, "plan oracle: first action without a winner");
+      const long slot = s * (n + 1) + a;
+      const int len = hl[o];
+      wl[slot] = len;
+      for (int i = 0; i < len; ++i) {
+        const int act = (i < L) ? field(hp + o * 6, i) : field(hp + o * 6 + 3, i - L);
+        TORCH_CHECK(act >= 1 && act <= n, "plan oracle: corrupt winner");
+        wp[slot * 16 + i] = act;
+      }
+    }
+  }
+  return {win_len, win_plan};
+}
+
 // Exhaustive plan oracle over a batch of S states (plan_oracle.hip).
 // Returns CPU tensors, one row per state and one slot per first action
 // (slot 0 = STOP, the empty plan; slot a = best plan starting with action a):
@@ -1118,50 +1174,10 @@ std::vector<torch::Tensor> plan_oracle_search(
               hipGetErrorString(launch_err));
 
   // ---- reduce the prefix winners by first action (host; not hot) ----
-  auto h_reward = item_reward.cpu();
-  auto h_len = item_len.cpu();
-  auto h_plan = item_plan.cpu();
+  auto [win_len, win_plan] =
+      reduce_oracle_winners(item_reward, item_len, item_plan, n, L, depth_lim);
   auto h_proc = proc.cpu();
   auto h_clean = clean.cpu();
-  const float* hr = h_reward.data_ptr<float>();
-  const int* hl = h_len.data_ptr<int>();
-  const unsigned* hp = reinterpret_cast<const unsigned*>(h_plan.data_ptr<int>());
-  auto cpu_i = torch::TensorOptions().dtype(torch::kInt32);
-  auto win_len = torch::zeros({S, (long)n + 1}, cpu_i);
-  auto win_plan = torch::zeros({S, (long)n + 1, 16}, cpu_i);
-  int* wl = win_len.data_ptr<int>();
-  int* wp = win_plan.data_ptr<int>();
-  auto field = [](const unsigned* w, int i) {
-    return (int)((w[i / 6] >> (5 * (i % 6))) & 31u);
-  };
-  for (long s = 0; s < S; ++s) {
-    std::vector<long> best(n + 1, -1);
-    for (long i = 0; i < n_prefix; ++i) {
-      const long o = s * n_prefix + i;
-      const int len = hl[o];
-      TORCH_CHECK(len >= 1 && len <= depth_lim,
-                  "plan oracle: no finite reward under a prefix "
-                  "(non-finite planner inputs?)");
-      const int a0 = field(hp + o * 6, 0);
-      TORCH_CHECK(a0 >= 1 && a0 <= n, "plan oracle: corrupt winner");
-      const long b = best[a0];
-      // items are in lexicographic prefix order: an equal (reward, len)
-      // keeps the earlier one
-      if (b < 0 || hr[o] > hr[b] || (hr[o] == hr[b] && len < hl[b])) best[a0] = o;
-    }
-    for (int a = 1; a <= n; ++a) {
-      const long o = best[a];
-      TORCH_CHECK(o >= 0, "plan oracle: first action without a winner");
-      const long slot = s * (n + 1) + a;
-      const int len = hl[o];
-      wl[slot] = len;
-      for (int i = 0; i < len; ++i) {
-        const int act = (i < L) ? field(hp + o * 6, i) : field(hp + o * 6 + 3, i - L);
-        TORCH_CHECK(act >= 1 && act <= n, "plan oracle: corrupt winner");
-        wp[slot * 16 + i] = act;
-      }
-    }
-  }
 
   // ---- reported rewards: eval_plan on the winners ----
   auto d_plans = win_plan.to(gscore.device());
@@ -1174,6 +1190,121 @@ std::vector<torch::Tensor> plan_oracle_search(
         gfiles.data_ptr<float>() + s * G, pproc[s], pclean[s], p,
         d_plans.data_ptr<int>() + s * (n + 1) * 16, n + 1, 16,
         d_reward.data_ptr<float>() + s * (n + 1), stream.stream());
+  }
+  auto win_reward = d_reward.cpu();
+  auto meta = torch::zeros({2}, torch::TensorOptions().dtype(torch::kInt64));
+  meta.data_ptr<int64_t>()[0] = L;
+  meta.data_ptr<int64_t>()[1] = n_prefix;
+  return {win_reward, win_len, win_plan, meta};
+}
+
+// Exhaustive oracle of the joint P-process MDP over a batch of S states
+// (plan_oracle_multi.hip); n = P + 1 + G non-STOP actions.  Outputs as
+// plan_oracle_search; the rewards are eval_plan_multi's value of the winners
+// (== mcts_multi_eval_plans).  Bad arguments raise ValueError before anything
+// launches, a per-state plan count above 2^31 - 1 among them: no call can
+// start a search that keeps the device for minutes.
+std::vector<torch::Tensor> plan_oracle_multi_search(
+    torch::Tensor gscore, torch::Tensor gmb, torch::Tensor gfiles,
+    torch::Tensor proc, torch::Tensor clean, pybind11::dict param_dict,
+    long prefix_len) {
+  const long G = param_dict["n_groups"].cast<long>();
+  const long D = param_dict["max_depth"].cast<long>();
+  TORCH_CHECK_VALUE(G >= 1 && G <= 16, "joint plan oracle: 1 <= G <= 16 (got ", G, ")");
+  TORCH_CHECK_VALUE(D >= 1 && D <= 16,
+                    "joint plan oracle: 1 <= max_depth <= 16 (got ", D, ")");
+  const torch::Tensor* ins[] = {&gscore, &gmb, &gfiles, &proc, &clean};
+  for (const torch::Tensor* t : ins) {
+    TORCH_CHECK_VALUE(t->is_cuda() && t->is_contiguous() &&
+                          t->scalar_type() == torch::kFloat32 &&
+                          t->get_device() == gscore.get_device(),
+                      "joint plan oracle: inputs must be contiguous f32 tensors "
+                      "on one GPU");
+  }
+  TORCH_CHECK_VALUE(gscore.dim() == 2 && gscore.size(1) == G &&
+                        gmb.sizes() == gscore.sizes() &&
+                        gfiles.sizes() == gscore.sizes(),
+                    "joint plan oracle: gscore/gmb/gfiles must all be [S, n_groups]");
+  const long S = gscore.size(0);
+  TORCH_CHECK_VALUE(S >= 1 && S <= (1 << 20), "joint plan oracle: 1 <= S <= 2^20 states");
+  TORCH_CHECK_VALUE(proc.dim() == 2 && proc.size(0) == S && clean.dim() == 1 &&
+                        clean.size(0) == S,
+                    "joint plan oracle: proc must be [S, P] and clean [S]");
+  const long P = proc.size(1);
+  TORCH_CHECK_VALUE(P >= 1 && P <= NERRF_MULTI_MAX_PROCS,
+                    "joint plan oracle: 1 <= P <= 8 (got ", P, ")");
+  const int n = (int)(P + 1 + G);  // non-STOP actions, <= 25
+  const int depth_lim = std::min((int)D, n);
+  // plans per state, exactly: 25!/9! overflows 64 bits, so count in 128
+  unsigned __int128 n_plans = 0, term = 1;
+  for (int k = 0; k <= depth_lim; ++k) {
+    n_plans += term;
+    term *= (unsigned __int128)(n - k);
+  }
+  const unsigned __int128 kMaxPlans = 2147483647;  // 2^31 - 1
+  TORCH_CHECK_VALUE(n_plans <= kMaxPlans, "joint plan oracle: P=", P, ", G=", G,
+                    ", max_depth=", D, " give about ", (double)n_plans,
+                    " plans per state, above the hard bound 2^31 - 1");
+  const long kMaxPrefix = 1L << 22;
+  int L = 1;
+  long n_prefix = n;
+  if (prefix_len > 0) {
+    TORCH_CHECK_VALUE(prefix_len <= depth_lim,
+                      "joint plan oracle: prefix_len must be <= min(max_depth, n)");
+    for (L = 1; L < prefix_len; ++L) n_prefix *= (n - L);
+    TORCH_CHECK_VALUE(n_prefix <= kMaxPrefix,
+                      "joint plan oracle: prefix_len gives too many prefixes");
+  } else {
+    // plan_oracle_search's fill target; n is larger here, so L comes out smaller
+    const int l_max = std::max(1, depth_lim - 3);
+    const long target = 65536;
+    while (L < l_max && S * n_prefix < target &&
+           n_prefix * (n - L) <= kMaxPrefix) {
+      n_prefix *= (n - L);
+      ++L;
+    }
+  }
+  TORCH_CHECK_VALUE(S * n_prefix <= (1L << 26),
+                    "joint plan oracle: too many work items (states x prefixes); "
+                    "lower prefix_len or split the batch");
+  auto p = params_from_dict(param_dict);
+  p.n_actions = n + 1;
+
+  auto opts_f = gscore.options().dtype(torch::kFloat32);
+  auto opts_i = gscore.options().dtype(torch::kInt32);
+  auto item_reward = torch::empty({S, n_prefix}, opts_f);
+  auto item_len = torch::empty({S, n_prefix}, opts_i);
+  auto item_plan = torch::empty({S, n_prefix, 6}, opts_i);
+  auto stream = at::hip::getCurrentHIPStream();
+  hipError_t err = nerrf::launch_plan_oracle_multi(
+      gscore.data_ptr<float>(), gmb.data_ptr<float>(), gfiles.data_ptr<float>(),
+      proc.data_ptr<float>(), clean.data_ptr<float>(), p, (int)P, (int)S, L,
+      (int)n_prefix, item_reward.data_ptr<float>(), item_len.data_ptr<int>(),
+      reinterpret_cast<unsigned*>(item_plan.data_ptr<int>()), stream.stream());
+  TORCH_CHECK(err == hipSuccess, "joint plan oracle launch failed: ",
+              hipGetErrorString(err));
+
+  auto [win_len, win_plan] =
+      reduce_oracle_winners(item_reward, item_len, item_plan, n, L, depth_lim);
+
+  // ---- reported rewards: eval_plan_multi on the winners ----
+  auto h_proc = proc.cpu();
+  auto h_clean = clean.cpu();
+  auto d_plans = win_plan.to(gscore.device());
+  auto d_reward = torch::empty({S, (long)n + 1}, opts_f);
+  nerrf::MultiPlannerParamsDev mp;
+  mp.base = p;
+  mp.n_procs = (int)P;
+  for (long s = 0; s < S; ++s) {
+    for (int q = 0; q < NERRF_MULTI_MAX_PROCS; ++q)
+      mp.proc_score[q] = q < P ? h_proc.data_ptr<float>()[s * P + q] : 0.0f;
+    err = nerrf::launch_mcts_multi_eval_plans(
+        gscore.data_ptr<float>() + s * G, gmb.data_ptr<float>() + s * G,
+        gfiles.data_ptr<float>() + s * G, h_clean.data_ptr<float>()[s], mp,
+        d_plans.data_ptr<int>() + s * (n + 1) * 16, n + 1, 16,
+        d_reward.data_ptr<float>() + s * (n + 1), stream.stream());
+    TORCH_CHECK(err == hipSuccess, "joint plan oracle: eval launch failed: ",
+                hipGetErrorString(err));
   }
   auto win_reward = d_reward.cpu();
   auto meta = torch::zeros({2}, torch::TensorOptions().dtype(torch::kInt64));
@@ -1205,6 +1336,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "batch plan reward evaluation of the P-process MDP");
   m.def("plan_oracle_search", &plan_oracle_search,
         "exhaustive best plan per first action over a batch of states",
+        pybind11::arg("gscore"), pybind11::arg("gmb"), pybind11::arg("gfiles"),
+        pybind11::arg("proc"), pybind11::arg("clean"), pybind11::arg("params"),
+        pybind11::arg("prefix_len") = 0);
+  m.def("plan_oracle_multi_search", &plan_oracle_multi_search,
+        "exhaustive best joint (P-process) plan per first action over a batch "
+        "of states",
         pybind11::arg("gscore"), pybind11::arg("gmb"), pybind11::arg("gfiles"),
         pybind11::arg("proc"), pybind11::arg("clean"), pybind11::arg("params"),
         pybind11::arg("prefix_len") = 0);

@@ -14,8 +14,10 @@ runs the batched HIP search (ops/hip/plan_oracle.hip) and re-scores the
 per-first-action winners in fp64.
 
 A `MultiPlannerState` (P processes, rewards.simulate_plan_multi) has
-n = P + 1 + G non-STOP actions and the same canonical form; its oracle runs
-on the CPU only.
+n = P + 1 + G non-STOP actions and the same canonical form (P=2, G=8, D=10:
+68 588 312 plans).  Both paths take it: the CPU reference scores it with
+`simulate_plan_multi`, and a GPU device runs ops/hip/plan_oracle_multi.hip.
+One GPU batch holds one kind of state and one (P, G).
 
 Tie-break (shared by both paths): among plans of equal reward the shorter plan
 wins, then the lexicographically smaller action tuple.
@@ -28,7 +30,7 @@ from typing import Dict, List, Optional, Sequence, Tuple, Union
 import numpy as np
 
 from .rewards import (A_STOP, MultiPlannerState, PlannerParams, PlannerState,
-                      plan_reward, simulate_plan)
+                      plan_reward)
 
 # Default cap of the CPU reference.  simulate_plan costs about 10 us per plan
 # in CPython on one core (13 700 plans: ~0.12 s), so 1e6 plans return in
@@ -36,6 +38,12 @@ from .rewards import (A_STOP, MultiPlannerState, PlannerParams, PlannerState,
 CPU_MAX_PLANS = 1_000_000
 # Default cap of the GPU search (see profiles/PROFILES.md for the measurement).
 GPU_MAX_PLANS = 2**31 - 1
+# Default cap of StreamingEngine.plan_joint(planner="exact") on a GPU.  The
+# largest D=10 joint state under it, P=4, G=8 (1 359 245 486 plans), measured
+# 8.7 ms per call on one MI355X (profiles/PROFILES.md, "Joint plan oracle"),
+# so the cap is not lowered; it is also the joint kernel's hard bound
+# (bindings.cpp refuses more).
+GPU_MAX_PLANS_JOINT = 2**31 - 1
 
 # "reward agrees with the fp64 truth": the project's tolerance for fp32
 # device rewards (tests/test_ops_gpu.py::test_mcts_eval_plans_matches_cpu)
@@ -121,8 +129,9 @@ def _check_state(state: PlannerState, params: PlannerParams) -> None:
 
 
 def _too_many(state: PlannerState, params: PlannerParams, n_plans: int, cap: int) -> ValueError:
+    procs = f"P={state.n_procs} processes and " if isinstance(state, MultiPlannerState) else ""
     return ValueError(
-        f"exhaustive planner: G={state.n_groups} groups at max_depth D={params.max_depth} "
+        f"exhaustive planner: {procs}G={state.n_groups} groups at max_depth D={params.max_depth} "
         f"give {n_plans} plans, above max_plans={cap}; lower max_depth or n_groups, "
         f"or use planner='mcts'"
     )
@@ -208,11 +217,16 @@ def _exhaustive_best_gpu(
 
     ext = load_extension(required=True)  # a missing kernel on GPU is an error
     g = states[0].n_groups
+    joint = isinstance(states[0], MultiPlannerState)
+    if any(isinstance(s, MultiPlannerState) != joint for s in states):
+        raise ValueError("one batch holds PlannerStates or MultiPlannerStates, not both")
     if g > MAX_GROUPS_DEV or params.max_depth > MAX_DEPTH_DEV:
         raise ValueError(f"GPU plan oracle supports G <= {MAX_GROUPS_DEV} and "
                          f"max_depth <= {MAX_DEPTH_DEV} (got G={g}, D={params.max_depth})")
     if any(s.n_groups != g for s in states):
         raise ValueError("all states of one batch must have the same number of groups")
+    if joint and any(s.n_procs != states[0].n_procs for s in states):
+        raise ValueError("all states of one batch must have the same number of processes")
     dev = torch.device(device)
 
     def stack(get) -> "torch.Tensor":
@@ -221,14 +235,15 @@ def _exhaustive_best_gpu(
     gs = stack(lambda s: s.group_score)
     gm = stack(lambda s: s.group_mb)
     gf = stack(lambda s: s.group_files)
-    pr = torch.tensor([float(s.proc_score) for s in states], dtype=torch.float32, device=dev)
+    pr = stack(lambda s: s.proc_score)  # [S], or [S, P] of a joint batch
     cl = torch.tensor([float(s.remaining_clean_mb) for s in states], dtype=torch.float32, device=dev)
-    w_reward, w_len, w_plan, _meta = ext.plan_oracle_search(
+    search = ext.plan_oracle_multi_search if joint else ext.plan_oracle_search
+    w_reward, w_len, w_plan, _meta = search(
         gs, gm, gf, pr, cl, _params_dict(g, params), int(prefix_len))
     w_reward = w_reward.numpy()
     w_len = w_len.numpy()
     w_plan = w_plan.numpy()
-    n = 2 + g
+    n = states[0].n_actions - 1
     n_plans = count_plans(n, params.max_depth)
     out = []
     for si, st in enumerate(states):
@@ -237,7 +252,7 @@ def _exhaustive_best_gpu(
         for a in range(0, n + 1):
             plan = [int(x) for x in w_plan[si, a, : int(w_len[si, a])]]
             # the final choice is made in fp64 among the <= n+1 winners
-            fab[a] = (float(simulate_plan(st, plan + [A_STOP], params)), plan)
+            fab[a] = (float(plan_reward(st, plan + [A_STOP], params)), plan)
             dev_r[a] = float(w_reward[si, a])
         reward, best = _pick(fab)
         out.append(OracleResult(plan=best, reward=reward, first_action_best=fab,
@@ -256,11 +271,13 @@ def exhaustive_best(
 
     On a GPU device the batched HIP search finds, per state, the best plan
     under each first action in fp32; those at most n+1 winners are re-scored
-    with `simulate_plan` in fp64 and the final plan is picked among them in
-    fp64 with the module's tie-break.  On "cpu" the reference runs (its own
-    cap, CPU_MAX_PLANS, applies as well).  Raises ValueError when the plan
-    count exceeds `max_plans` and on non-finite inputs.  `prefix_len`
-    overrides the GPU work decomposition (0 = automatic)."""
+    with the state's reward (`plan_reward`) in fp64 and the final plan is
+    picked among them in fp64 with the module's tie-break.  On "cpu" the
+    reference runs (its own cap, CPU_MAX_PLANS, applies as well).  A GPU batch
+    holds PlannerStates or MultiPlannerStates, not both, and one (P, G).
+    Raises ValueError on a batch that does not, when the plan count exceeds
+    `max_plans`, and on non-finite inputs.  `prefix_len` overrides the GPU
+    work decomposition (0 = automatic)."""
     params = params or PlannerParams()
     single = isinstance(state_or_states, (PlannerState, MultiPlannerState))
     states = [state_or_states] if single else list(state_or_states)
@@ -272,8 +289,6 @@ def exhaustive_best(
         if n_plans > max_plans:
             raise _too_many(st, params, n_plans, max_plans)
     dev = str(device)
-    if dev != "cpu" and any(isinstance(st, MultiPlannerState) for st in states):
-        raise ValueError("the plan oracle of a MultiPlannerState runs on device='cpu' only")
     if dev == "cpu" or params.max_depth < 1:
         res = [exhaustive_best_cpu(st, params, max_plans=min(max_plans, CPU_MAX_PLANS)) for st in states]
     else:
@@ -315,7 +330,7 @@ def plans_under(first_action: int, n_actions_nonstop: int, max_depth: int) -> in
 
 
 __all__ = [
-    "CPU_MAX_PLANS", "GPU_MAX_PLANS",
+    "CPU_MAX_PLANS", "GPU_MAX_PLANS", "GPU_MAX_PLANS_JOINT",
     "OracleResult", "REWARD_ATOL", "REWARD_RTOL", "canonical_plan", "count_plans",
     "exhaustive_best", "exhaustive_best_cpu", "plan_regret", "plans_under", "reward_tol",
 ]

@@ -649,15 +649,23 @@ class StreamingEngine:
         return res
 
     def plan_joint(self, det: Detection, culprits: Optional[List[int]] = None,
-                   n_sims: int = 1024, use_gpu: Optional[bool] = None) -> JointPlanResult:
+                   n_sims: int = 1024, use_gpu: Optional[bool] = None,
+                   planner: str = "mcts", max_plans: Optional[int] = None) -> JointPlanResult:
         """One plan against several culprits at once: one KILL per process,
         RESTORE, the damage cap and the depth budget shared between them.
+
+        planner="mcts" (default) searches with `n_sims` simulations;
+        planner="exact" enumerates every joint plan (planner/oracle.py) and
+        raises ValueError when the plan space exceeds `max_plans` (default:
+        GPU_MAX_PLANS_JOINT on the GPU, CPU_MAX_PLANS with use_gpu=False).
 
         `culprits` are process keys (default: those of det.culprits, in their
         order, at most 8).  Each one's attributed files are bucketed by score
         as in build_state into its share of planner_params.n_groups; files of
         no chosen culprit are not planned over and come back as `unplanned`.
         ValueError when no chosen culprit has an attributed file."""
+        if planner not in ("mcts", "exact"):
+            raise ValueError(f"unknown planner {planner!r}: expected 'mcts' or 'exact'")
         if culprits is None:
             keys = [c.proc for c in det.culprits][:MAX_PROCS]
         else:
@@ -695,7 +703,10 @@ class StreamingEngine:
             remaining_clean_mb=clean_mb, group_owner=np.array(owner, dtype=np.int64))
         if use_gpu is None:
             use_gpu = self.device.type == "cuda"
-        if use_gpu:
+        if planner == "exact":
+            # plan_joint reads only planner_params and device of `self`
+            res = StreamingEngine._plan_exact(self, state, use_gpu, max_plans)
+        elif use_gpu:
             res = run_mcts_multi_gpu(state, self.planner_params, n_sims=n_sims, device=str(self.device))
         else:
             res = run_mcts_multi(state, self.planner_params, n_sims=n_sims)
@@ -708,14 +719,16 @@ class StreamingEngine:
     def _plan_exact(self, state, use_gpu: bool, max_plans: Optional[int]) -> PlanResult:
         """Exhaustive planner: the oracle's plan, with the exact root action
         values Q*(a) in place of MCTS visit statistics."""
-        from ..planner.oracle import GPU_MAX_PLANS, exhaustive_best, plans_under
+        from ..planner.oracle import (GPU_MAX_PLANS, GPU_MAX_PLANS_JOINT, exhaustive_best,
+                                      plans_under)
 
         params = self.planner_params
+        cap = GPU_MAX_PLANS_JOINT if isinstance(state, MultiPlannerState) else GPU_MAX_PLANS
         orc = exhaustive_best(
             state, params, device=str(self.device) if use_gpu else "cpu",
-            max_plans=GPU_MAX_PLANS if max_plans is None else max_plans,
+            max_plans=cap if max_plans is None else max_plans,
         )
-        n = 2 + state.n_groups
+        n = state.n_actions - 1
         ranked = sorted(
             [(int(a), float(q), plans_under(a, n, params.max_depth))
              for a, (q, _plan) in orc.first_action_best.items()],
