@@ -12,7 +12,8 @@ Commands (spec: reference ROADMAP.md:86, README.md:82 — `nerrf undo`,
   nerrf train ...                    training entrypoint (= ai/train.py)
   nerrf serve --trace T              tracker-sim + streaming engine demo
   nerrf plan-quality --states N      MCTS regret against the exhaustive plan oracle
-                                     (--procs P: the joint planner and oracle)
+                                     (--procs P: the joint planner and oracle;
+                                     --oracle sets: search over action sets, P <= 8)
 
 Entry point: `python -m nerrf_amd.cli <cmd>` (also installed as ./nerrf).
 """
@@ -167,7 +168,7 @@ def cmd_plan_quality(args) -> int:
     sims = [int(x) for x in args.sims.split(",") if x]
     report = measure_plan_quality(args.states, args.seed, sims=sims,
                                   device=args.device, params=params,
-                                  n_procs=args.procs)
+                                  n_procs=args.procs, oracle=args.oracle)
     print(json.dumps(report, indent=2))
     return 0
 
@@ -311,8 +312,9 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--trace", default=None, help="trace file to ingest first")
     p.add_argument("--device", default="cpu")
     p.add_argument("--sims", type=int, default=1024)
-    p.add_argument("--planner", choices=("mcts", "exact"), default="mcts",
-                   help="exact = exhaustive search over every plan")
+    p.add_argument("--planner", choices=("mcts", "exact", "sets"), default="mcts",
+                   help="exact = exhaustive search over every plan; "
+                        "sets = the same optimum by search over action sets")
     p.add_argument("--force", action="store_true")
     p.add_argument("--checkpoint", default=None, help="trained model checkpoint dir")
 
@@ -322,8 +324,9 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--file-kb", type=int, default=32)
     p.add_argument("--device", default="cpu")
     p.add_argument("--sims", type=int, default=512)
-    p.add_argument("--planner", choices=("mcts", "exact"), default="mcts",
-                   help="exact = exhaustive search over every plan")
+    p.add_argument("--planner", choices=("mcts", "exact", "sets"), default="mcts",
+                   help="exact = exhaustive search over every plan; "
+                        "sets = the same optimum by search over action sets")
 
     p = sub.add_parser("plan-quality",
                        help="MCTS regret against the exhaustive plan oracle")
@@ -339,6 +342,9 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--procs", type=int, default=1,
                    help="culprit processes P; above 1 measures the joint planner "
                         "against the joint oracle")
+    p.add_argument("--oracle", choices=("exact", "sets"), default="exact",
+                   help="exact = enumerate every plan (P <= 4 at the defaults); "
+                        "sets = search over action sets, any P <= 8")
 
     p = sub.add_parser("serve", help="streaming engine (live tracker or trace demo)")
     p.add_argument("--trace", default=None, help="trace file (demo mode)")

@@ -30,6 +30,11 @@ hipError_t launch_plan_oracle_multi(const float*, const float*, const float*,
                                     const float*, const float*,
                                     const PlannerParamsDev&, int, int, int,
                                     int, float*, int*, unsigned*, hipStream_t);
+hipError_t launch_plan_subsets(const float*, const float*, const float*,
+                               const float*, const float*,
+                               const PlannerParamsDev&, int, int, int,
+                               unsigned long long*, unsigned long long*,
+                               hipStream_t);
 void launch_gather_mean_fwd(const void*, const long*, const float*, void*, int,
                             int, int, bool, hipStream_t);
 void launch_gather_mean_bwd(const void*, const long*, const float*, float*,
@@ -1313,6 +1318,124 @@ std::vector<torch::Tensor> plan_oracle_multi_search(
   return {win_reward, win_len, win_plan, meta};
 }
 
+// Subset-lattice search of the joint P-process MDP over a batch of S states
+// (plan_subsets.hip): the exact best plan per first action as a maximum over
+// sets of actions, so no plan-count bound applies.  Inputs and outputs as
+// plan_oracle_multi_search; meta is (chunk_log, units per state).  Bad
+// arguments raise ValueError before anything launches.
+std::vector<torch::Tensor> plan_subsets_search(
+    torch::Tensor gscore, torch::Tensor gmb, torch::Tensor gfiles,
+    torch::Tensor proc, torch::Tensor clean, pybind11::dict param_dict) {
+  const long G = param_dict["n_groups"].cast<long>();
+  const long D = param_dict["max_depth"].cast<long>();
+  TORCH_CHECK_VALUE(G >= 1 && G <= 16, "subset plan search: 1 <= G <= 16 (got ", G, ")");
+  // eval_plan_multi, which reports the winners' rewards, takes plans of <= 16
+  TORCH_CHECK_VALUE(D >= 1 && D <= 16,
+                    "subset plan search: 1 <= max_depth <= 16 (got ", D, ")");
+  const torch::Tensor* ins[] = {&gscore, &gmb, &gfiles, &proc, &clean};
+  for (const torch::Tensor* t : ins) {
+    TORCH_CHECK_VALUE(t->is_cuda() && t->is_contiguous() &&
+                          t->scalar_type() == torch::kFloat32 &&
+                          t->get_device() == gscore.get_device(),
+                      "subset plan search: inputs must be contiguous f32 tensors "
+                      "on one GPU");
+  }
+  TORCH_CHECK_VALUE(gscore.dim() == 2 && gscore.size(1) == G &&
+                        gmb.sizes() == gscore.sizes() &&
+                        gfiles.sizes() == gscore.sizes(),
+                    "subset plan search: gscore/gmb/gfiles must all be [S, n_groups]");
+  const long S = gscore.size(0);
+  TORCH_CHECK_VALUE(S >= 1, "subset plan search: needs at least one state");
+  TORCH_CHECK_VALUE(proc.dim() == 2 && proc.size(0) == S && clean.dim() == 1 &&
+                        clean.size(0) == S,
+                    "subset plan search: proc must be [S, P] and clean [S]");
+  const long P = proc.size(1);
+  TORCH_CHECK_VALUE(P >= 1 && P <= NERRF_MULTI_MAX_PROCS,
+                    "subset plan search: 1 <= P <= 8 (got ", P, ")");
+  const int n = (int)(P + 1 + G);  // non-STOP actions, <= 25
+  const int depth_lim = std::min((int)D, n);
+  // a unit (kill mask, chunk of the revert masks) is one wave's work: split
+  // the 2^G revert masks until the device has waves to fill, and keep at
+  // least one mask per lane
+  const long kMaxRows = 1L << 20, kTargetUnits = 4096;
+  TORCH_CHECK_VALUE((S << P) <= kMaxRows,
+                    "subset plan search: too many states for one batch (S * 2^P "
+                    "must be <= 2^20); split the batch");
+  int chunk_log = 0;
+  while (chunk_log < G - 6 && (S << (P + chunk_log)) < kTargetUnits) ++chunk_log;
+  const long n_units = 1L << (P + chunk_log);
+  auto p = params_from_dict(param_dict);
+  p.n_actions = n + 1;
+
+  auto opts_k = gscore.options().dtype(torch::kInt64);
+  auto rows = torch::empty({S, n_units, 18}, opts_k);
+  auto d_keys = torch::empty({S, (long)n + 1}, opts_k);
+  auto stream = at::hip::getCurrentHIPStream();
+  hipError_t err = nerrf::launch_plan_subsets(
+      gscore.data_ptr<float>(), gmb.data_ptr<float>(), gfiles.data_ptr<float>(),
+      proc.data_ptr<float>(), clean.data_ptr<float>(), p, (int)P, (int)S,
+      chunk_log, reinterpret_cast<unsigned long long*>(rows.data_ptr<int64_t>()),
+      reinterpret_cast<unsigned long long*>(d_keys.data_ptr<int64_t>()),
+      stream.stream());
+  TORCH_CHECK(err == hipSuccess, "subset plan search launch failed: ",
+              hipGetErrorString(err));
+
+  // ---- expand the winning set masks: a, then the rest ascending ----
+  auto h_keys = d_keys.cpu();
+  const int64_t* hk = h_keys.data_ptr<int64_t>();
+  auto cpu_i = torch::TensorOptions().dtype(torch::kInt32);
+  auto win_len = torch::zeros({S, (long)n + 1}, cpu_i);
+  auto win_plan = torch::zeros({S, (long)n + 1, 16}, cpu_i);
+  int* wl = win_len.data_ptr<int>();
+  int* wp = win_plan.data_ptr<int>();
+  for (long s = 0; s < S; ++s) {
+    for (int a = 1; a <= n; ++a) {
+      const long slot = s * (n + 1) + a;
+      const uint64_t key = (uint64_t)hk[slot];
+      TORCH_CHECK(key != 0, "subset plan search: first action without a winner");
+      const unsigned lo = (unsigned)(key & 0xFFFFFFFFu);
+      unsigned mask = 0;  // bit i of the key's low 25 is action 25 - i
+      for (int i = 0; i < 25; ++i)
+        if ((lo >> i) & 1u) mask |= 1u << (25 - i);
+      const int len = 31 - (int)((lo >> 25) & 31u);
+      TORCH_CHECK(len >= 1 && len <= depth_lim && len == __builtin_popcount(mask) &&
+                      ((mask >> a) & 1u) && (mask >> (n + 1)) == 0u,
+                  "subset plan search: corrupt winner (non-finite planner inputs?)");
+      wl[slot] = len;
+      int* plan = wp + slot * 16;
+      int i = 0;
+      plan[i++] = a;
+      for (int act = 1; act <= n; ++act)
+        if (act != a && ((mask >> act) & 1u)) plan[i++] = act;
+    }
+  }
+
+  // ---- reported rewards: eval_plan_multi on the winners ----
+  auto h_proc = proc.cpu();
+  auto h_clean = clean.cpu();
+  auto d_plans = win_plan.to(gscore.device());
+  auto d_reward = torch::empty({S, (long)n + 1}, gscore.options());
+  nerrf::MultiPlannerParamsDev mp;
+  mp.base = p;
+  mp.n_procs = (int)P;
+  for (long s = 0; s < S; ++s) {
+    for (int q = 0; q < NERRF_MULTI_MAX_PROCS; ++q)
+      mp.proc_score[q] = q < P ? h_proc.data_ptr<float>()[s * P + q] : 0.0f;
+    err = nerrf::launch_mcts_multi_eval_plans(
+        gscore.data_ptr<float>() + s * G, gmb.data_ptr<float>() + s * G,
+        gfiles.data_ptr<float>() + s * G, h_clean.data_ptr<float>()[s], mp,
+        d_plans.data_ptr<int>() + s * (n + 1) * 16, n + 1, 16,
+        d_reward.data_ptr<float>() + s * (n + 1), stream.stream());
+    TORCH_CHECK(err == hipSuccess, "subset plan search: eval launch failed: ",
+                hipGetErrorString(err));
+  }
+  auto win_reward = d_reward.cpu();
+  auto meta = torch::zeros({2}, torch::TensorOptions().dtype(torch::kInt64));
+  meta.data_ptr<int64_t>()[0] = chunk_log;
+  meta.data_ptr<int64_t>()[1] = n_units;
+  return {win_reward, win_len, win_plan, meta};
+}
+
 }  // namespace
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
@@ -1345,6 +1468,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         pybind11::arg("gscore"), pybind11::arg("gmb"), pybind11::arg("gfiles"),
         pybind11::arg("proc"), pybind11::arg("clean"), pybind11::arg("params"),
         pybind11::arg("prefix_len") = 0);
+  m.def("plan_subsets_search", &plan_subsets_search,
+        "exact best joint (P-process) plan per first action over a batch of "
+        "states, by search over action sets",
+        pybind11::arg("gscore"), pybind11::arg("gmb"), pybind11::arg("gfiles"),
+        pybind11::arg("proc"), pybind11::arg("clean"), pybind11::arg("params"));
   m.def("gather_mean_fwd", &gather_mean_fwd, "weighted neighbor gather-mean");
   m.def("gather_mean_bwd", &gather_mean_bwd, "gather-mean backward");
   m.def("gather_mean_bwd_csr", &gather_mean_bwd_csr,

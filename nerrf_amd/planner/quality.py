@@ -36,7 +36,7 @@ from typing import Dict, List, Optional, Sequence
 import numpy as np
 
 from .mcts import run_mcts, run_mcts_gpu, run_mcts_multi, run_mcts_multi_gpu
-from .oracle import exhaustive_best, plan_regret, reward_tol
+from .oracle import exhaustive_best, plan_regret, reward_tol, subset_best
 from .rewards import (MAX_GROUPS, MAX_PROCS, MultiPlannerState, PlannerParams, PlannerState,
                       build_state)
 
@@ -101,13 +101,19 @@ def measure_plan_quality(
     params: Optional[PlannerParams] = None,
     mcts_seed: int = 1,
     n_procs: int = 1,
+    oracle: str = "exact",
 ) -> Dict:
     """Regret of the MCTS planner at each simulation budget, against the
     exhaustive oracle, over `n_states` generated states.  On a GPU device both
     the oracle and MCTS run their HIP kernels.  `n_procs` > 1 measures the
     joint planner on joint states; the report then carries "n_procs", and its
-    "n_groups" is the states' G."""
+    "n_groups" is the states' G.  `oracle` "exact" enumerates every plan
+    (exhaustive_best, with its plan-count cap); "sets" searches action sets
+    (subset_best: any P <= 8), and "plans_per_state" then counts sets."""
+    if oracle not in ("exact", "sets"):
+        raise ValueError(f"unknown oracle {oracle!r}: expected 'exact' or 'sets'")
     params = params or PlannerParams()
+    best = exhaustive_best if oracle == "exact" else subset_best
     states = generate_states(n_states, seed, params.n_groups, n_procs)
     on_gpu = str(device) != "cpu"
     if n_procs == 1:
@@ -118,10 +124,10 @@ def measure_plan_quality(
     if on_gpu:
         import torch
 
-        exhaustive_best(states[:1], params, device=device)  # warm-up: module load
+        best(states[:1], params, device=device)  # warm-up: module load
         torch.cuda.synchronize()
     t0 = time.perf_counter()
-    oracles = exhaustive_best(states, params, device=device)
+    oracles = best(states, params, device=device)
     oracle_s = time.perf_counter() - t0
     report: Dict = {
         "states": len(states),
@@ -133,6 +139,8 @@ def measure_plan_quality(
         "oracle_s_per_state": oracle_s / max(len(states), 1),
         "budgets": {},
     }
+    if oracle != "exact":
+        report["oracle"] = oracle
     if n_procs > 1:
         report["n_procs"] = int(n_procs)
         report["n_groups"] = states[0].n_groups if states else 0

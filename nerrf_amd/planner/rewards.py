@@ -206,6 +206,11 @@ def simulate_plan_multi(
     Mirrors `eval_plan_multi` in ops/hip/mcts_multi.hip.  `live` is summed in
     ascending p from zero after every KILL (never decremented), so host and
     device add in one order.  For P = 1 the value equals `simulate_plan`'s.
+
+    The search over action sets (oracle.subset_best, ops/hip/plan_subsets.hip)
+    relies on this function's structure: everything but `ongoing` depends only
+    on the set of executed actions, a KILL adds nothing to `ongoing`, and the
+    loss never decreases in it.  A change that breaks any of these breaks it.
     """
     g = state.n_groups
     n_procs = state.n_procs

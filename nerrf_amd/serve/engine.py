@@ -613,13 +613,14 @@ class StreamingEngine:
              culprit: Optional[int] = None) -> PlanResult:
         """planner="mcts" (default) searches with `n_sims` simulations;
         planner="exact" enumerates every plan (planner/oracle.py) and raises
-        ValueError when the plan space exceeds `max_plans`.
+        ValueError when the plan space exceeds `max_plans`; planner="sets"
+        finds the same optimum by search over action sets, without a cap.
 
         `culprit` (a process key of det.proc_scores) plans against that one
         process: only the files det.file_culprit attributes to it, and its own
         node score; ValueError when no file is attributed to it."""
-        if planner not in ("mcts", "exact"):
-            raise ValueError(f"unknown planner {planner!r}: expected 'mcts' or 'exact'")
+        if planner not in ("mcts", "exact", "sets"):
+            raise ValueError(f"unknown planner {planner!r}: expected 'mcts', 'exact' or 'sets'")
         if culprit is None:
             paths = list(det.file_scores.keys())
             proc = max(det.proc_scores.values(), default=0.0)
@@ -640,6 +641,8 @@ class StreamingEngine:
             use_gpu = self.device.type == "cuda"
         if planner == "exact":
             res = self._plan_exact(state, use_gpu, max_plans)
+        elif planner == "sets":
+            res = self._plan_sets(state, use_gpu)
         elif use_gpu:
             res = run_mcts_gpu(state, self.planner_params, n_sims=n_sims, device=str(self.device))
         else:
@@ -658,14 +661,16 @@ class StreamingEngine:
         planner="exact" enumerates every joint plan (planner/oracle.py) and
         raises ValueError when the plan space exceeds `max_plans` (default:
         GPU_MAX_PLANS_JOINT on the GPU, CPU_MAX_PLANS with use_gpu=False).
+        planner="sets" finds the same optimum by search over action sets
+        (oracle.subset_best): exact at any P <= 8 and G <= 16, no cap.
 
         `culprits` are process keys (default: those of det.culprits, in their
         order, at most 8).  Each one's attributed files are bucketed by score
         as in build_state into its share of planner_params.n_groups; files of
         no chosen culprit are not planned over and come back as `unplanned`.
         ValueError when no chosen culprit has an attributed file."""
-        if planner not in ("mcts", "exact"):
-            raise ValueError(f"unknown planner {planner!r}: expected 'mcts' or 'exact'")
+        if planner not in ("mcts", "exact", "sets"):
+            raise ValueError(f"unknown planner {planner!r}: expected 'mcts', 'exact' or 'sets'")
         if culprits is None:
             keys = [c.proc for c in det.culprits][:MAX_PROCS]
         else:
@@ -706,6 +711,8 @@ class StreamingEngine:
         if planner == "exact":
             # plan_joint reads only planner_params and device of `self`
             res = StreamingEngine._plan_exact(self, state, use_gpu, max_plans)
+        elif planner == "sets":
+            res = StreamingEngine._plan_sets(self, state, use_gpu)
         elif use_gpu:
             res = run_mcts_multi_gpu(state, self.planner_params, n_sims=n_sims, device=str(self.device))
         else:
@@ -731,6 +738,23 @@ class StreamingEngine:
         n = state.n_actions - 1
         ranked = sorted(
             [(int(a), float(q), plans_under(a, n, params.max_depth))
+             for a, (q, _plan) in orc.first_action_best.items()],
+            key=lambda t: (-t[1], t[0]),
+        )
+        return PlanResult(plan=list(orc.plan), ranked_actions=ranked,
+                          root_value=float(orc.reward), simulations=int(orc.n_plans))
+
+    def _plan_sets(self, state, use_gpu: bool) -> PlanResult:
+        """Subset planner: the exact plan and root action values Q*(a) of
+        oracle.subset_best; each action's count is the sets that can start
+        with it, `simulations` the sets of the state."""
+        from ..planner.oracle import sets_under, subset_best
+
+        params = self.planner_params
+        orc = subset_best(state, params, device=str(self.device) if use_gpu else "cpu")
+        n = state.n_actions - 1
+        ranked = sorted(
+            [(int(a), float(q), sets_under(a, n, params.max_depth))
              for a, (q, _plan) in orc.first_action_best.items()],
             key=lambda t: (-t[1], t[0]),
         )

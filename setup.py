@@ -27,6 +27,7 @@ sources = [
     os.path.join(HIP_DIR, "mcts_multi.hip"),
     os.path.join(HIP_DIR, "plan_oracle.hip"),
     os.path.join(HIP_DIR, "plan_oracle_multi.hip"),
+    os.path.join(HIP_DIR, "plan_subsets.hip"),
     os.path.join(HIP_DIR, "event_scatter.hip"),
     os.path.join(HIP_DIR, "sage_fused.hip"),
     os.path.join(HIP_DIR, "sage_ln_act.hip"),
